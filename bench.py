@@ -1,7 +1,18 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mcells/s through SMRF progressive_filter on a 16384^2 fp32 DEM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 16384] [--windows 50]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 16384] [--windows 50] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, checks the object count, writes its outputs with --dump-outputs
+and prints the line: headline fields, ``config`` and the arithmetic part of ``roofline``.  Everything that takes runs
+of its own - the roofline's classes / live counters / power / device copy rate, ``secondary`` and ``cpu_baseline`` -
+runs only with ``--full`` (the --no-* options below then leave parts of it out).
+
+``--dump-outputs DIR`` (after the timed steps): the bool mask the last timed step returned, as float32 0 / 1 -
+``DIR/mask.npy`` (rows x cols) when it has at most 8 Mi cells, else ``DIR/mask_sample.npy`` at up to 4 Mi fixed flat
+indices (``DIR/mask_sample_index.npy``, float64, from ``default_rng(20240)``) - beside ``DIR/mask_row_sums.npy`` and
+``DIR/mask_col_sums.npy`` (float64, every cell of the mask); 48 MiB at most.  The DEM is seeded, so two builds run
+with the same arguments can be compared file for file.
 
 A "step" is one call of the public drop-in ``neilpy_amd.progressive_filter(Z, windows, cellsize,
 slope_threshold)`` (all windows: erosion + dilation + flagging per window, plus the call's own NaN
@@ -21,7 +32,8 @@ device times (max over ranks per step), ``ms_per_step`` their MEDIAN and ``value
 ``roofline`` (dominant kernels: smrf::ring_kernel, two passes per window, and the fused small-disk launches):
   achieved      algorithmic bytes per pass ((5s + 2) / 2 B/cell, a pass = half a window) / median device
                 time per pass; frac = achieved / 8 TB/s
-  traffic       HBM bytes per pass from the hardware counters (two rocprofv3 --pmc child runs after the timed region);
+  traffic       HBM bytes per pass from the hardware counters (--full: two rocprofv3 --pmc child runs after the timed
+                region; a plain run quotes profiles/pmc_summary.json);
                 frac_traffic = traffic / time per pass / peak - the physical rate; it is below `frac` because the
                 fused launches move 10 B/cell per window where the convention credits 22
   classes       one extra step through smrf_progressive_filter_timed_* (an event per window): windows grouped by how
@@ -72,7 +84,74 @@ def parse():
                     help="gloo stages halos through the host: for rehearsing N>1 ranks on one GPU")
     ap.add_argument("--share-gpu", action="store_true", help="all ranks use cuda:0 (rehearsal on a one-GPU box)")
     ap.add_argument("--launch-timeout", type=int, default=1500, help="bare --gpus N: seconds the self-started ranks may take")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's mask to DIR as .npy")
+    ap.add_argument("--full", action="store_true", help="also the measurements that take runs of their own: roofline classes, "
+                    "live counters, power, device copy rate, secondary block, CPU baseline")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+def host_dem(n, dtype, b0, b1, workers):
+    """Rows [b0, b1) of ``synth_dem(n, seed=20240)``.  synth_dem's row bands are exactly the rows of the full DEM
+    (its random fields are keyed per 256-row block), so with ``workers`` > 1 the bands of 1024 rows are made in fresh
+    child processes (spawned: they never touch the GPU) - the same array, sooner (~12 s serially at 16384^2)."""
+    from neilpy_amd.synth import synth_dem
+    band = 1024
+    if workers <= 1 or b1 - b0 < 2 * band:
+        return synth_dem(n, seed=20240, dtype=dtype, row_range=(b0, b1))
+    import multiprocessing as mp
+    from concurrent.futures import ProcessPoolExecutor
+    cuts = [b0] + list(range((b0 // band + 1) * band, b1, band)) + [b1]
+    out = np.empty((b1 - b0, n), dtype=dtype)
+    with ProcessPoolExecutor(workers, mp_context=mp.get_context("spawn")) as ex:
+        futs = [(r0, r1, ex.submit(synth_dem, n, seed=20240, dtype=dtype, row_range=(r0, r1)))
+                for r0, r1 in zip(cuts[:-1], cuts[1:])]
+        for r0, r1, f in futs:
+            out[r0 - b0:r1 - b0] = f.result()
+    return out
+
+
+DUMP_FULL_CELLS = 8 << 20                                   # up to this many cells the whole mask is written
+DUMP_SAMPLE = 4 << 20                                       # else the mask at this many fixed flat indices
+
+
+def dump_outputs(out_dir, mask, n, b0, b1, world, cdev):
+    """--dump-outputs: the mask the last timed step returned (this rank's rows [b0, b1) of the n x n raster), as float32
+    0 / 1, whole or at a fixed seeded sample of flat indices, plus its float64 row and column sums.  With N > 1 ranks
+    every rank contributes its rows through an all-reduce (sum) and rank 0 writes the files."""
+    import torch
+    import torch.distributed as dist
+    cells = n * n
+    m = mask.reshape(b1 - b0, n).to(torch.float32)
+    rows = torch.zeros(n, dtype=torch.float64, device=m.device)
+    rows[b0:b1] = m.sum(dim=1, dtype=torch.float64)
+    cols = m.sum(dim=0, dtype=torch.float64)
+    arrays = {"mask_row_sums": rows, "mask_col_sums": cols}
+    if cells <= DUMP_FULL_CELLS:
+        full = torch.zeros((n, n), dtype=torch.float32, device=m.device)
+        full[b0:b1] = m
+        arrays["mask"] = full
+    else:
+        idx = np.unique(np.random.default_rng(20240).integers(0, cells, DUMP_SAMPLE))
+        mine = (idx >= b0 * n) & (idx < b1 * n)
+        samp = torch.zeros(idx.size, dtype=torch.float32, device=m.device)
+        sel = torch.from_numpy(np.flatnonzero(mine)).to(m.device)
+        samp[sel] = m.reshape(-1)[torch.from_numpy(idx[mine] - b0 * n).to(m.device)]
+        arrays["mask_sample"] = samp
+        arrays["mask_sample_index"] = idx.astype(np.float64)
+    if world > 1:
+        for k, v in arrays.items():
+            if torch.is_tensor(v):
+                t = v.to(cdev)
+                dist.all_reduce(t, op=dist.ReduceOp.SUM)
+                arrays[k] = t
+    if dist.is_initialized() and dist.get_rank() != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v.cpu().numpy() if torch.is_tensor(v) else v)
 
 
 def cpu_baseline(Z_crop, windows, cellsize, slope):
@@ -400,10 +479,10 @@ def main():
     cellsize, slope = 1, .15
     thresholds = slope * (windows * cellsize)
     b0, b1 = sharded.band_rows(n, world, rank)
-    Z_host = neilpy_amd.synth_dem(n, seed=20240, dtype=np_dtype, row_range=(b0, b1))
+    Z_host = host_dem(n, np_dtype, b0, b1, max(1, min(8, len(os.sched_getaffinity(0))) // world))
     Z = torch.from_numpy(Z_host).to(dev)
     crop = None
-    if rank == 0 and world == 1 and not a.no_cpu and a.cpu_crop > 0:   # the CPU figure belongs to the N = 1 line only
+    if a.full and rank == 0 and world == 1 and not a.no_cpu and a.cpu_crop > 0:   # the CPU figure: N = 1 line only
         c = min(a.cpu_crop, n, b1 - b0)
         crop = np.ascontiguousarray(Z_host[:c, :c])
     del Z_host
@@ -437,8 +516,10 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     step_ms = np.array([evs[k].elapsed_time(evs[k + 1]) for k in range(a.steps)], dtype=np.float64)
-    power = power_leg(step, barrier, dev) if world == 1 and not a.no_power else None
     n_obj = int(mask.sum().item())
+    if a.dump_outputs:                                    # before any later step can reuse the mask's buffers
+        dump_outputs(a.dump_outputs, mask, n, b0, b1, world, dev if a.backend == "nccl" else "cpu")
+    power = power_leg(step, barrier, dev) if a.full and world == 1 and not a.no_power else None
     per_rank = None
     if world > 1:
         exch_ms = np.array([sum(e0.elapsed_time(e1) for e0, e1 in evl) for evl, _ in xev], dtype=np.float64)
@@ -475,7 +556,7 @@ def main():
     # (torch's copy_; what hand-written streaming kernels reach by access width, grid and plane size is
     # tools/ubench/stream_rate.hip -> profiles/r04_stream_rate_ubench.md)
     copy_gbps = None
-    if rank == 0:
+    if a.full and rank == 0:
         tmp = torch.empty_like(Z)
         c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         tmp.copy_(Z)
@@ -499,12 +580,12 @@ def main():
         avg_launch_s = ms_median / 1e3 / launches
         achieved = alg_bytes_launch / avg_launch_s / 1e9
         classes, window_ms = (None, None)
-        if world == 1:
+        if a.full and world == 1:
             classes, window_ms = window_classes(Z, windows, thresholds, cells, elem, peak)
         traffic, traffic_source = None, None
         pmc = os.path.join(ROOT, "profiles", "pmc_summary.json")
         live, valu = None, None
-        if world == 1 and not a.no_pmc:
+        if a.full and world == 1 and not a.no_pmc:
             # the timed region is over: release this process's planes first, the child runs need the same HBM
             del mask
             Z = None
@@ -549,7 +630,7 @@ def main():
                                    "one or several windows in one launch); %d passes per step, achieved = algorithmic bytes per "
                                    "pass / median device time per pass" % launches,
                          "algorithmic_bytes_per_launch": alg_bytes_launch, "avg_launch_ms": avg_launch_s * 1e3,
-                         "device_copy_gbps": copy_gbps, "frac_of_device_copy": achieved / copy_gbps,
+                         "device_copy_gbps": copy_gbps, "frac_of_device_copy": achieved / copy_gbps if copy_gbps else None,
                          "classes": classes, "window_ms": window_ms},
         }
         if power is not None:
@@ -585,7 +666,7 @@ def main():
                                                   "frac_moved: the bytes each launch class moves; frac_traffic: FETCH_SIZE + WRITE_SIZE")
         if per_rank is not None:
             out["per_rank"] = per_rank
-        if world == 1 and not a.no_secondary and (n, a.windows, a.dtype) == (16384, 50, "f32"):
+        if a.full and world == 1 and not a.no_secondary and (n, a.windows, a.dtype) == (16384, 50, "f32"):
             try:
                 Z = None
                 torch.cuda.empty_cache()

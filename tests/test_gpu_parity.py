@@ -342,17 +342,23 @@ def test_sharded_two_ranks_on_one_gpu(nz, tmp_path):
     import sys
     from conftest import ROOT
     common = ["--size", "1024", "--windows", "12", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-pmc", "--no-secondary"]
-    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + common,
-                         capture_output=True, text=True, timeout=600)
+    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full",
+                          "--dump-outputs", str(tmp_path / "one")] + common, capture_output=True, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
     # NO launcher and no WORLD_SIZE in the environment: bench.py starts its own two ranks (fresh children under
     # torch.distributed.run), relays rank 0's line and its exit code
     bare_env = {k: v for k, v in os.environ.items()
                 if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "LOCAL_WORLD_SIZE")}
-    two = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu"]
-                         + common, capture_output=True, text=True, timeout=600, env=bare_env)
+    two = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu",
+                          "--dump-outputs", str(tmp_path / "two")] + common, capture_output=True, text=True, timeout=600,
+                         env=bare_env)
     assert two.returncode == 0, two.stderr[-2000:]
     assert len([l for l in two.stdout.splitlines() if l.startswith("{")]) == 1      # ONE line
+    # --dump-outputs: the two ranks' bands make the single device's mask, file for file
+    names = sorted(os.listdir(tmp_path / "one"))
+    assert "mask.npy" in names and sorted(os.listdir(tmp_path / "two")) == names
+    for f in names:
+        assert np.array_equal(np.load(tmp_path / "one" / f), np.load(tmp_path / "two" / f)), f
     j1 = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][-1])
     j2 = json.loads([l for l in two.stdout.splitlines() if l.startswith("{")][-1])
     assert j2["n_gpus"] == 2 and j1["config"]["object_cells"] == j2["config"]["object_cells"]
@@ -369,6 +375,31 @@ def test_sharded_two_ranks_on_one_gpu(nz, tmp_path):
     for pr in j2["per_rank"]:
         assert pr["exchanges"] == sh["exchanges_per_step"] and pr["exchange_ms"] > 0 and pr["compute_ms"] > 0
         assert pr["exchange_bytes_sent"] == sum(sh["halo_rows_per_exchange"]) * 1024 * 4
+
+
+def test_bench_plain_run_dumps_the_mask(nz, gpu_device, tmp_path):
+    """a plain run (no --full) times exactly --steps steps, leaves the extra measurements out and, with --dump-outputs,
+    writes the mask its last step returned: the drop-in call's mask on the same seeded DEM"""
+    import json
+    import subprocess
+    import sys
+    import torch
+    from conftest import ROOT
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--size", "1024", "--windows", "12",
+                        "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path)], capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["steps"] == 4 and len(j["step_ms"]) == 4 and j["ms_per_step"] > 0
+    assert j["unit"] == "Mcells/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+    assert "secondary" not in j and "cpu_baseline" not in j and "power" not in j["roofline"]
+    assert j["roofline"]["classes"] is None and j["roofline"]["device_copy_gbps"] is None
+    Z = torch.from_numpy(nz.synth_dem(1024, seed=20240)).to(gpu_device)
+    want = nz.progressive_filter(Z, np.arange(1, 13), 1, .15).cpu().numpy()
+    got = np.load(tmp_path / "mask.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, want.astype(np.float32))
+    assert int(got.sum()) == j["config"]["object_cells"]
+    assert np.array_equal(np.load(tmp_path / "mask_row_sums.npy"), want.sum(1))
 
 
 def test_bench_bare_multi_gpu_preflight(nz):
