@@ -29,6 +29,9 @@
  *                             RectBivariateSpline(...).ev and the point test, neilpy/neilpy.py:1768-1795
  *   smrf_negate_f64, smrf_mask_apply_f64
  *                             the elementwise glue of smrf(), neilpy/neilpy.py:1744, :1748, :1762-1763
+ *   smrf_terrain_rays_*       openness(), skyview_factor(), count_openness(), geomorphons() and
+ *                             ternary_pattern_from_openness(), neilpy/neilpy.py:1290-1653 (host side:
+ *                             neilpy_amd/terrain.py)
  *
  * Conventions
  *   - every pointer named d_* is DEVICE memory (hipMalloc or a torch CUDA tensor's data_ptr);
@@ -344,6 +347,40 @@ SMRF_API int smrf_negate_f64(const double* d_in, double* d_out, int64_t n, void*
 /* u = a | b | c (b, c, d_union may be NULL); Z[u] = NaN  (neilpy.py:1748 and :1762-1763) */
 SMRF_API int smrf_mask_apply_f64(double* d_Z, const uint8_t* d_a, const uint8_t* d_b, const uint8_t* d_c,
                         uint8_t* d_union, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * terrain ray marches (neilpy_amd/terrain.py)
+ * ------------------------------------------------------------------------------------------ */
+#define SMRF_TERRAIN_OPENNESS 0   /* openness(), neilpy.py:1325-1357 -> d_out0 float64 degrees */
+#define SMRF_TERRAIN_SKYVIEW 1    /* skyview_factor(), neilpy.py:1360-1384 -> d_out0 float64 */
+#define SMRF_TERRAIN_COUNT 2      /* count_openness() / geomorphons(), neilpy.py:1600-1653 -> d_out0 num_pos,
+                                     d_out1 num_neg, d_out2 geomorphon class (uint8 each, any of them NULL) */
+#define SMRF_TERRAIN_TERNARY 3    /* ternary_pattern_from_openness(), neilpy.py:1404-1428 -> d_out0 int64 code */
+#define SMRF_TERRAIN_IMPL_AUTO 0    /* = TILED */
+#define SMRF_TERRAIN_IMPL_TILED 1   /* workgroup tile + halo of min(max_step, cap) cells in LDS, longer steps from global */
+#define SMRF_TERRAIN_IMPL_DIRECT 2  /* every sample from global memory; same bits as TILED */
+#define SMRF_TERRAIN_HALO_CAP_F32 40
+#define SMRF_TERRAIN_HALO_CAP_F64 24
+#define SMRF_TERRAIN_OPT_NEGATIVE 1 /* TERNARY: use_negative_openness */
+#define SMRF_TERRAIN_OPT_ENHANCE 2  /* COUNT: geomorphons(enhance=True)'s second count and correction (:1640-1649) */
+
+/* One launch of the ray-march family over a rows x cols raster d_Z (contiguous).  For each direction d in dir_mask
+ * (bit d; d = 0..7 clockwise from the upper left, ashift at neilpy.py:1290-1307) and each step i < nsteps the slope
+ * t = fp64(Z[sample] - Z[cell]) / d_dist[(d & 1) * nsteps + i] is taken at distance d_steps[i] (ascending, >= 1;
+ * max_step >= the largest; d_dist holds (cellsize * k) * sqrt(2) for even d, then cellsize * k for odd d, as the
+ * host computes it).  Off-raster samples read the cell itself (openness family) or the last on-raster cell of the
+ * ray (SKYVIEW).  d_flags[i]: bit 0 = the step belongs to the main march, bit 1 = to the enhance march (COUNT; other
+ * modes use every step).  OPENNESS: mean over d_neighbors[0..n_neighbors) of the per-direction angle, in degrees.
+ * COUNT / TERNARY compare each direction's positive minus negative openness with +-threshold (degrees); d_lut is the
+ * 9 x 9 uint8 table [num_pos][num_neg] (COUNT with d_out2) or NULL / 6561 int64 lowest-equivalent codes (TERNARY). */
+SMRF_API int smrf_terrain_rays_f32(const float* d_Z, int rows, int cols, int mode, const int* d_steps,
+                          const uint8_t* d_flags, const double* d_dist, int nsteps, int max_step,
+                          const int* d_neighbors, int n_neighbors, int dir_mask, double threshold, int options,
+                          const void* d_lut, void* d_out0, void* d_out1, void* d_out2, int impl, void* stream);
+SMRF_API int smrf_terrain_rays_f64(const double* d_Z, int rows, int cols, int mode, const int* d_steps,
+                          const uint8_t* d_flags, const double* d_dist, int nsteps, int max_step,
+                          const int* d_neighbors, int n_neighbors, int dir_mask, double threshold, int options,
+                          const void* d_lut, void* d_out0, void* d_out1, void* d_out2, int impl, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,8 @@
 Drop-in for ``neilpy.smrf`` / ``progressive_filter`` / ``create_dem`` /
 ``inpaint_nans_by_springs`` (and the ``disk`` / ``opening`` seam they use).  All compute runs
 in hand-written gfx950 HIP kernels in ``libsmrf_hip.so`` (C ABI: ``include/smrf_hip.h``);
-there is no CPU fallback.
+there is no CPU fallback.  ``openness`` / ``skyview_factor`` / ``geomorphons`` and their kin (neilpy_amd/terrain.py)
+analyse the resulting DTM with the same kernels-only rule.
 """
 from ._lib import SmrfHipError, load as load_library, LIB_PATH          # noqa: F401
 from .affine import Affine, edges_from_IT, from_origin, write_worldfile                 # noqa: F401
@@ -12,5 +13,8 @@ from .api import (create_dem, dilation, disk, erosion, inpaint_nans_by_fda, inpa
                   opening, progressive_filter, pssm, smrf)
 from .las import read_las, read_las_xyz, write_las                         # noqa: F401
 from .synth import synth_dem, synth_points                               # noqa: F401
+from .terrain import (count_openness, geomorphon_cmap, geomorphons, get_lowest_equivalent, int2base,   # noqa: F401
+                      openness, progressive_window, skyview_factor, ternary_pattern_from_openness,
+                      terrain_code_to_geomorphon)
 
 __version__ = "0.1.0"

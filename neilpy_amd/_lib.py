@@ -13,6 +13,10 @@ LIB_PATH = os.environ.get("NEILPY_AMD_LIB") or os.path.join(_HERE, "_lib", "libs
 IMPL_AUTO, IMPL_RING, IMPL_DIRECT = 0, 1, 2
 ROUTE_TWO_PASS, ROUTE_FUSED, ROUTE_DIRECT, ROUTE_COPY, ROUTE_CHAIN = 0, 1, 2, 3, 4
 RING_MAX_RADIUS = 64
+# terrain ray marches (include/smrf_hip.h): impl= of neilpy_amd.terrain, halo caps of the LDS tile, modes
+TERRAIN_IMPL_AUTO, TERRAIN_IMPL_TILED, TERRAIN_IMPL_DIRECT = 0, 1, 2
+TERRAIN_HALO_CAP = {"f32": 40, "f64": 24}
+TERRAIN_OPENNESS, TERRAIN_SKYVIEW, TERRAIN_COUNT, TERRAIN_TERNARY = 0, 1, 2, 3
 
 
 class SmrfHipError(RuntimeError):
@@ -76,6 +80,8 @@ SIGNATURES = {
     "smrf_classify_points_f64": (_i, [_p, _p, _p, _i64, _d, _d, _p, _p]),
     "smrf_negate_f64": (_i, [_p, _p, _i64, _p]),
     "smrf_mask_apply_f64": (_i, [_p, _p, _p, _p, _p, _i64, _p]),
+    "smrf_terrain_rays_f32": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, _p, _i, _i, _d, _i, _p, _p, _p, _p, _i, _p]),
+    "smrf_terrain_rays_f64": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, _p, _i, _i, _d, _i, _p, _p, _p, _p, _i, _p]),
 }
 
 _lib = None
