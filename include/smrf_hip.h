@@ -32,6 +32,9 @@
  *   smrf_terrain_rays_*       openness(), skyview_factor(), count_openness(), geomorphons() and
  *                             ternary_pattern_from_openness(), neilpy/neilpy.py:1290-1653 (host side:
  *                             neilpy_amd/terrain.py)
+ *   smrf_surface_*            slope(), aspect(), hillshade(), multiple_illumination(), esri_slope(), curvature(),
+ *                             esri_curvature(), zevenbergen_and_thorne_curvature(), evans_curvature() and
+ *                             wilson_gallant_curvature(), neilpy/neilpy.py:434-842 (host side: neilpy_amd/surface.py)
  *
  * Conventions
  *   - every pointer named d_* is DEVICE memory (hipMalloc or a torch CUDA tensor's data_ptr);
@@ -381,6 +384,38 @@ SMRF_API int smrf_terrain_rays_f64(const double* d_Z, int rows, int cols, int mo
                           const uint8_t* d_flags, const double* d_dist, int nsteps, int max_step,
                           const int* d_neighbors, int n_neighbors, int dir_mask, double threshold, int options,
                           const void* d_lut, void* d_out0, void* d_out1, void* d_out2, int impl, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * local surface derivatives: 3 x 3 stencils (neilpy_amd/surface.py)
+ * ------------------------------------------------------------------------------------------ */
+#define SMRF_SURFACE_SLOPE 0      /* slope(), neilpy.py:456 -> d_out0 T; p0 = cellsize / z_factor */
+#define SMRF_SURFACE_ASPECT 1     /* aspect(), :471 -> d_out0 T; p0 = the value of flat cells (flat_as, NaN allowed) */
+#define SMRF_SURFACE_HILLSHADE 2  /* hillshade() / multiple_illumination(), :814 / :830; p0 = cellsize / z_factor ->
+                                     d_out0 uint8 max over the angle table, d_out1 float64 H (one angle only) */
+#define SMRF_SURFACE_HORN 3       /* esri_slope(), :434 -> d_out0 T; p0 = cellsize, p1 = z_factor */
+#define SMRF_SURFACE_LAPLACE 4    /* curvature(), :487 -> d_out0 T; p0 = cellsize */
+#define SMRF_SURFACE_ESRI 5       /* esri_curvature(), :520 -> K, K_plan, K_profile; p0 = L**2, p1 = 4*(L**2), p2 = 2*L */
+#define SMRF_SURFACE_ZT 6         /* zevenbergen_and_thorne_curvature(), :596 -> K, K_profile, K_plan, K_tan, K_long,
+                                     K_cross; parameters as ESRI */
+#define SMRF_SURFACE_EVANS 7      /* evans_curvature(), :671 -> the same six; p0 = 6*L**2, p1 = 3*L**2, p2 = 4*L**2,
+                                     p3 = 6*L */
+#define SMRF_SURFACE_WG 8         /* wilson_gallant_curvature(), :753 -> K, Kp, Kc, Kt; p0 = 2*H, p1 = H**2 */
+#define SMRF_SURFACE_OPT_RADIANS 1  /* SLOPE: arctan of the gradient norm */
+#define SMRF_SURFACE_OPT_DEGREES 2  /* SLOPE, ASPECT, HORN: in degrees (np.rad2deg) */
+
+/* One launch over a rows x cols raster d_Z (contiguous).  p0..p3 are the mode's parameters, formed by the host with the
+ * reference's expressions and rounded to T in the kernel.  Edge rules: np.gradient's (SLOPE, ASPECT, HILLSHADE; rows,
+ * cols >= 2), ndimage 'reflect' (HORN, LAPLACE) and ashift's, an off-raster neighbour read as the cell (the other
+ * curvatures).  Multi-output modes write every non-NULL d_out* (up to six, in the reference's return order) from one
+ * read of d_Z; outputs beyond the mode's count must be NULL.  HILLSHADE: d_angles is a device table of n_angles rows
+ * (cos zenith, sin zenith, azimuth in radians; float64, computed as the reference computes them); d_out0 gets the
+ * largest uint8 shade over the rows, d_out1 (n_angles = 1) the float64 shade. */
+SMRF_API int smrf_surface_f32(const float* d_Z, int rows, int cols, int mode, int options, double p0, double p1,
+                     double p2, double p3, const double* d_angles, int n_angles, void* d_out0, void* d_out1,
+                     void* d_out2, void* d_out3, void* d_out4, void* d_out5, void* stream);
+SMRF_API int smrf_surface_f64(const double* d_Z, int rows, int cols, int mode, int options, double p0, double p1,
+                     double p2, double p3, const double* d_angles, int n_angles, void* d_out0, void* d_out1,
+                     void* d_out2, void* d_out3, void* d_out4, void* d_out5, void* stream);
 
 #ifdef __cplusplus
 }

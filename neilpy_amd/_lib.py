@@ -17,6 +17,10 @@ RING_MAX_RADIUS = 64
 TERRAIN_IMPL_AUTO, TERRAIN_IMPL_TILED, TERRAIN_IMPL_DIRECT = 0, 1, 2
 TERRAIN_HALO_CAP = {"f32": 40, "f64": 24}
 TERRAIN_OPENNESS, TERRAIN_SKYVIEW, TERRAIN_COUNT, TERRAIN_TERNARY = 0, 1, 2, 3
+# surface derivatives (include/smrf_hip.h): modes and options of smrf_surface_*
+(SURFACE_SLOPE, SURFACE_ASPECT, SURFACE_HILLSHADE, SURFACE_HORN, SURFACE_LAPLACE, SURFACE_ESRI, SURFACE_ZT,
+ SURFACE_EVANS, SURFACE_WG) = range(9)
+SURFACE_OPT_RADIANS, SURFACE_OPT_DEGREES = 1, 2
 
 
 class SmrfHipError(RuntimeError):
@@ -82,6 +86,8 @@ SIGNATURES = {
     "smrf_mask_apply_f64": (_i, [_p, _p, _p, _p, _p, _i64, _p]),
     "smrf_terrain_rays_f32": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, _p, _i, _i, _d, _i, _p, _p, _p, _p, _i, _p]),
     "smrf_terrain_rays_f64": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, _p, _i, _i, _d, _i, _p, _p, _p, _p, _i, _p]),
+    "smrf_surface_f32": (_i, [_p, _i, _i, _i, _i, _d, _d, _d, _d, _p, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "smrf_surface_f64": (_i, [_p, _i, _i, _i, _i, _d, _d, _d, _d, _p, _i, _p, _p, _p, _p, _p, _p, _p]),
 }
 
 _lib = None
