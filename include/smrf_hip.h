@@ -194,6 +194,13 @@ SMRF_API int smrf_progressive_filter_timed_f64(const double* d_Z, int rows, int 
                                 uint8_t* d_when_dropped, void* d_workspace, size_t workspace_bytes, int nan_aware,
                                 int impl, void* stream, float* h_window_ms, int32_t* h_window_route);
 
+/* Which windows of the calling host thread's latest smrf_progressive_filter_* call took their erosion from the window
+ * before (e_R = min(erode(e_{R-1}, cross), leftover cells of the opened surface): bit-identical to the ring erosion; taken
+ * for a two-pass window whose radius is the previous two-pass window's + 1 on a raster without NaN, switch SMRF_ERO_INC =
+ * 0 never / 1 per measured table / 2 always).  Writes n bytes (0 / 1; 0 beyond the call's windows) and returns the
+ * call's window count.  Such a window still reports SMRF_ROUTE_TWO_PASS: it is two launches, 3s + (3s + 2) B/cell. */
+SMRF_API int smrf_pf_ero_inc_windows(uint8_t* h_taken, int n);
+
 /* number of NaN cells of a contiguous array, written to *h_count (synchronises `stream`) */
 SMRF_API int smrf_count_nan_f32(const float* d_a, int64_t n, int64_t* h_count, void* stream);
 SMRF_API int smrf_count_nan_f64(const double* d_a, int64_t n, int64_t* h_count, void* stream);

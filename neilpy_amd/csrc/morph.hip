@@ -267,6 +267,9 @@ int chain_flag_api(const T* last, T* opened, uint8_t* mask, uint8_t* when, const
   else return smrf_chain_f64(pat, c, (hipStream_t)stream);
 }
 
+// which windows of this host thread's latest progressive_filter call took the incremental erosion (smrf_pf_ero_inc_windows)
+thread_local std::vector<uint8_t> g_ero_inc_taken;
+
 template <typename T>
 int progressive_filter_api(const T* Z, int rows, int cols, const int32_t* windows, const double* thr, int nwin,
                            uint8_t* mask, uint8_t* when, void* ws, size_t ws_bytes, int nan_aware, int impl,
@@ -280,7 +283,12 @@ int progressive_filter_api(const T* Z, int rows, int cols, const int32_t* window
     if (windows[i] < 0) return smrf_fail(SMRF_E_ARG, "negative window %d", windows[i]);
   const size_t plane = (size_t)rows * cols;
   T* E = reinterpret_cast<T*>(ws);
-  T* O[2] = {E + plane, E + 2 * plane};
+  // Three planes whose roles rotate: pe holds the latest two-pass window's eroded surface, pl the surface `last` (-1: Z),
+  // and a launch writes its opened surface (the incremental erosion: its eroded one) into a plane that is neither.
+  T* P[3] = {E, E + plane, E + 2 * plane};
+  int pe = 0, pl = -1;
+  auto spare = [&]() { for (int k = 0; k < 3; ++k) if (k != pe && k != pl) return k; return 0; };
+  g_ero_inc_taken.assign((size_t)nwin, 0);
   // The first window's flag step writes every mask / when byte (DiskArgs::dense), so the planes are not cleared first:
   // one coalesced byte per cell instead of a memset pass plus scattered single-byte stores (window 0 flags the most cells)
   if (nwin == 0) {
@@ -297,7 +305,7 @@ int progressive_filter_api(const T* Z, int rows, int cols, const int32_t* window
                          (impl == SMRF_IMPL_AUTO || impl == SMRF_IMPL_RING);
   const int pat0 = may_chain ? smrf_chain_match((int)sizeof(T), windows, nwin, fuse_mode0 == 2 ? (1ll << 62) : (long long)plane) : -1;
   // the flag of a speculative first launch: the first word of the workspace's E plane, which nothing touches before the
-  // first two-pass window's erosion (chained / fused launches write O[0], O[1] only) - no allocation on this path
+  // first two-pass window's erosion (chained / fused launches never write plane pe = 0) - no allocation on this path
   unsigned* d_nan = nullptr;
   if (nan_aware < 0) {
     if (pat0 >= 0 && smrf_chain_halo(pat0) < rows) {
@@ -345,11 +353,17 @@ int progressive_filter_api(const T* Z, int rows, int cols, const int32_t* window
   const int fuse_mode = smrf_sw().fused;
   const bool fuse_ok0 = (impl == SMRF_IMPL_AUTO || impl == SMRF_IMPL_RING) && fuse_mode != 0;
   const bool chain_ok0 = smrf_sw().chain != 0;
-  int flip = 0;                                          // which of the two opened planes the next launch writes
+  // window R's erosion from window R-1's (morph_incero.h): e_R = min(erode(e_{R-1}, cross), min over the
+  // leftover cells P_R of last).  For window i when the raster has no NaN (scipy's NaN rule lives in the ring kernels), impl is
+  // auto or ring, windows[i] = windows[i-1] + 1, window i-1 ran as two ring passes (its eroded plane is still in the
+  // workspace) and an instance exists for the radius; SMRF_ERO_INC: 0 = never, 1 = where the measured table says it wins,
+  // 2 = every such window.  The identity holds on any raster size (tests/test_ero_inc.py), so there is no size condition.
+  const int inc_mode = smrf_sw().ero_inc;
+  int ring_two_pass_at = -2;                             // the latest window that ran as two ring passes
   for (int i = 0; i < nwin;) {
     const int r = windows[i];
-    T* opened = O[flip];
-    flip ^= 1;
+    const int po = spare();
+    T* opened = P[po];
     const bool fuse_ok = !nan_aware && fuse_ok0;           // (nan_aware can change once: a speculative first launch that met a NaN)
     const bool chain_ok = fuse_ok && chain_ok0;
     const int pat = chain_ok ? smrf_chain_match((int)sizeof(T), windows + i, nwin - i, fuse_mode == 2 ? (1ll << 62) : (long long)plane) : -1;
@@ -378,12 +392,12 @@ int progressive_filter_api(const T* Z, int rows, int cols, const int32_t* window
         d_nan = nullptr;
         if (h) {                                           // start over with scipy's NaN rule (two-pass kernels only)
           nan_aware = 1;
-          flip = 0;
+          pe = 0; pl = -1;
           last = Z;
           continue;                                        // i is still 0
         }
       }
-      if (nwin > 1) last = opened;
+      if (nwin > 1) { last = opened; pl = po; }
       for (int k = 0; k < len; ++k)                        // the chain's time lands on its first window, the others read ~0
         if (int rc = window_done(i + k, SMRF_ROUTE_CHAIN + k)) return rc;
       i += len;
@@ -395,17 +409,38 @@ int progressive_filter_api(const T* Z, int rows, int cols, const int32_t* window
     // R = 14 equal; 4096^2 and below +3 ... +20 %: profiles/r05_logs/segments/min_cells_fused.log); 48 Mi until then
     if (fuse_ok && smrf_fused_radius((int)sizeof(T), r) && (r <= 8 || fuse_mode == 2 || plane >= ((size_t)20 << 20))) {
       if (int rc = open_flag_api<T>(last, opened, mask, when, thr[i], i, rows, cols, cols, 0, rows, 0, rows, r, stream_, i == 0)) return rc;
-      if (nwin > 1) last = opened;
+      if (nwin > 1) { last = opened; pl = po; }
       if (int rc = window_done(i, SMRF_ROUTE_FUSED)) return rc;
       ++i;
       continue;
     }
-    if (int rc = disk_filter_api<T>(last, E, rows, cols, cols, 0, rows, 0, rows, r, 0, nan_aware, impl, stream_)) return rc;
-    if (int rc = dilate_flag_api<T>(E, last, opened, mask, when, thr[i], i, rows, cols, cols, 0, rows, 0, rows, r,
-                                    nan_aware, impl, stream_, i == 0))
-      return rc;
-    if (nwin > 1) last = opened;                        // neilpy.py:1675-1676
     const int eff = impl == SMRF_IMPL_AUTO ? (r <= SMRF_RING_MAX_RADIUS ? SMRF_IMPL_RING : SMRF_IMPL_DIRECT) : impl;
+    const bool inc = inc_mode != 0 && !nan_aware && eff == SMRF_IMPL_RING && i > 0 && ring_two_pass_at == i - 1 && pl >= 0 &&
+                     r == windows[i - 1] + 1 && smrf_inc_erode_has((int)sizeof(T), r) &&
+                     (inc_mode == 2 || smrf_inc_erode_adopted((int)sizeof(T), r));
+    if (inc) {
+      // e_R goes into the spare plane (it held opened_{R-2}), then opened_R goes over e_{R-1}
+      if constexpr (sizeof(T) == 4) {
+        if (int rc = smrf_inc_erode_f32(P[pe], last, P[po], rows, cols, cols, r, nt_rule<T>(rows, cols), stream)) return rc;
+      } else {
+        return smrf_fail(SMRF_E_HIP, "internal: no incremental erosion at this dtype");
+      }
+      opened = P[pe];
+      if (int rc = dilate_flag_api<T>(P[po], last, opened, mask, when, thr[i], i, rows, cols, cols, 0, rows, 0, rows, r,
+                                      nan_aware, impl, stream_, 0))
+        return rc;
+      last = opened;
+      pl = pe;
+      pe = po;
+      g_ero_inc_taken[(size_t)i] = 1;
+    } else {
+      if (int rc = disk_filter_api<T>(last, P[pe], rows, cols, cols, 0, rows, 0, rows, r, 0, nan_aware, impl, stream_)) return rc;
+      if (int rc = dilate_flag_api<T>(P[pe], last, opened, mask, when, thr[i], i, rows, cols, cols, 0, rows, 0, rows, r,
+                                      nan_aware, impl, stream_, i == 0))
+        return rc;
+      if (nwin > 1) { last = opened; pl = po; }           // neilpy.py:1675-1676
+    }
+    if (eff == SMRF_IMPL_RING && r >= 1) ring_two_pass_at = i;
     if (int rc = window_done(i, r == 0 ? SMRF_ROUTE_COPY : eff == SMRF_IMPL_RING ? SMRF_ROUTE_TWO_PASS : SMRF_ROUTE_DIRECT)) return rc;
     ++i;
   }
@@ -481,6 +516,12 @@ int smrf_pf_chain_flag_f64(const double* d_last, double* d_opened, uint8_t* d_ma
                            void* stream) {
   return chain_flag_api<double>(d_last, d_opened, d_mask, d_when_dropped, h_radii, h_thresholds, h_window_index, n_windows,
                                 img_rows, cols, ld, in_row0, in_rows, out_row0, out_rows, stream);
+}
+int smrf_pf_ero_inc_windows(uint8_t* h_taken, int n) {
+  if (!h_taken || n < 0) return smrf_fail(SMRF_E_ARG, "null h_taken");
+  const int have = (int)g_ero_inc_taken.size();
+  for (int i = 0; i < n; ++i) h_taken[i] = i < have ? g_ero_inc_taken[(size_t)i] : 0;
+  return have;
 }
 size_t smrf_progressive_filter_workspace_bytes(int rows, int cols, int elem_size) {
   return (size_t)3 * (size_t)rows * (size_t)cols * (size_t)elem_size;

@@ -46,6 +46,8 @@ struct SmrfSwitches {
   int xcd_remap;      // SMRF_XCD_REMAP=0: no XCD-aware tile placement in the ring kernels (A/B runs)
   int ring_slope;     // SMRF_RING_SLOPE: permille of segment length per residency class (-1 = the library's rule, 0 = equal segments)
   int ring_debug;     // SMRF_RING_DEBUG: print each instance's geometry once
+  int ero_inc;        // SMRF_ERO_INC: window R's erosion from window R-1's (morph_incero.h): 0 never, 1 where ero_inc_adopt.inc says
+                      // it wins (default), 2 every eligible window
 };
 SMRF_HIDDEN const SmrfSwitches& smrf_sw();
 
@@ -109,6 +111,12 @@ constexpr bool smrf_fused_radius(int elem_size, int r) {
   if (r < 1 || r > SMRF_FUSED_MAX_RADIUS) return false;
   return elem_size == 4 ? (r != 9) : (r <= 6);
 }
+// incremental erosion of progressive_filter's consecutive windows (morph_incero.h, defined in incero.hip): has = an instance
+// exists for this dtype and radius, adopted = the measured per-radius table takes it (csrc/ero_inc_adopt.inc)
+SMRF_HIDDEN bool smrf_inc_erode_has(int elem_size, int radius);
+SMRF_HIDDEN bool smrf_inc_erode_adopted(int elem_size, int radius);
+SMRF_HIDDEN int smrf_inc_erode_f32(const float* e_prev, const float* last, float* out, int rows, int cols, long long ld,
+                                   int radius, int nt, hipStream_t s);
 #define SMRF_RING_PARTS 8
 #define SMRF_RING_DECL(P)                                                                     \
   SMRF_HIDDEN int smrf_ring_f32_p##P(const DiskArgs<float>&, int mode, hipStream_t);          \

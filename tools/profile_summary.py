@@ -56,7 +56,8 @@ def stats(path, n, out):
 
 def stats3(path, n, out, elem=4):
     """Round 3 form: chain / fused / ring launches, every launch priced at the bytes it really moves per cell (a chain of
-    k windows 2s + 2k, a fused window 2s + 2, a ring erosion 2s, a ring dilation + flag 3s + 2: no GB/s above the peak),
+    k windows 2s + 2k, a fused window 2s + 2, a ring erosion 2s, an incremental erosion 3s, a ring dilation + flag 3s + 2: no
+    GB/s above the peak),
     beside SURVEY 8d's convention (5s + 2 per window, half of it per pass)."""
     rows = list(csv.DictReader(open(path)))
     tot = sum(float(r["TotalDurationNs"]) for r in rows)
@@ -65,6 +66,7 @@ def stats3(path, n, out, elem=4):
     for r in rows:
         k = r["Name"]
         m = (re.search(r"(ring_kernel)<(\w+), (\d+), (true|false)", k) or re.search(r"(fused_open_kernel)<(\w+), (\d+)", k) or
+             re.search(r"(inc_erode_kernel)<(\w+), (\d+)", k) or
              re.search(r"(chain_kernel)<(\w+), \d+, \d+, (\d+), (\d+), (\d+), (\d+)", k))
         if not m:
             other.append(r)
@@ -75,6 +77,10 @@ def stats3(path, n, out, elem=4):
             dil = g[3] == "true"
             hot.append((int(g[2]), 1 if dil else 0, "ring dilation + flag" if dil else "ring erosion", 1, (3 * elem + 2) if dil else 2 * elem,
                         avg, calls))
+        elif g[0] == "inc_erode_kernel":
+            # window R's erosion from window R-1's (csrc/morph_incero.h): reads e_{R-1} and the opened surface, writes e_R:
+            # 3s here, and with the unchanged dilation + flag (3s + 2) the window moves 6s + 2 B/cell
+            hot.append((int(g[2]), 0, "incremental erosion", 1, 3 * elem, avg, calls))
         elif g[0] == "fused_open_kernel":
             hot.append((int(g[2]), 0, "fused opening + flag", 2, 2 * elem + 2, avg, calls))
         else:
@@ -86,7 +92,7 @@ def stats3(path, n, out, elem=4):
     passes = sum(h[3] * h[6] for h in hot)
     moved = sum(h[4] * cells * h[6] for h in hot)
     lines = ["# rocprofv3 --kernel-trace --stats summary (bench.py, %dx%d %s)" % (n, n, "fp32" if elem == 4 else "fp64"), "",
-             "total kernel time %.3f ms; progressive_filter kernels (chain / fused / ring) %.3f ms (%.1f %%), %d launches = %d passes "
+             "total kernel time %.3f ms; progressive_filter kernels (chain / fused / ring / incremental erosion) %.3f ms (%.1f %%), %d launches = %d passes "
              "(a pass = half a window; a fused launch is 2, a chain of k windows 2k), average per pass %.4f ms"
              % (tot / 1e6, ht / 1e6, 100 * ht / tot, sum(h[6] for h in hot), passes, ht / passes / 1e6), "",
              "SURVEY 8d convention: %d B/cell per pass = %.3f GB -> %.0f GB/s over all passes (frac %.3f of 8 TB/s)"
