@@ -1,0 +1,52 @@
+"""progressive_filter through the C ABI with everything the routing tests look at (shared by test_gpu_ero_inc.py and
+test_gpu_incero_edges.py), and the rule of csrc/morph.hip for which windows take the incremental erosion."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+
+
+def run_pf(Zd, windows, nan_aware=-1, impl=0):
+    """(mask, when, the workspace's three planes, route per window, took the incremental erosion per window)"""
+    import torch
+    from neilpy_amd import _lib
+    lib = _lib.load()
+    rows, cols = Zd.shape
+    win = np.ascontiguousarray(np.asarray(windows, dtype=np.int32))
+    thr = np.ascontiguousarray(.15 * (win * 1.0))
+    sfx = "f32" if Zd.dtype == torch.float32 else "f64"
+    nbytes = lib.smrf_progressive_filter_workspace_bytes(rows, cols, Zd.element_size())
+    ws = torch.zeros(nbytes, dtype=torch.uint8, device=Zd.device)
+    mask = torch.empty((rows, cols), dtype=torch.uint8, device=Zd.device)
+    when = torch.empty((rows, cols), dtype=torch.uint8, device=Zd.device)
+    ms = np.zeros(win.size, dtype=np.float32)
+    route = np.zeros(win.size, dtype=np.int32)
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    fn = getattr(lib, "smrf_progressive_filter_timed_" + sfx)
+    _lib.check(fn(C.c_void_p(Zd.data_ptr()), rows, cols, win.ctypes.data_as(C.c_void_p), thr.ctypes.data_as(C.c_void_p),
+                  int(win.size), C.c_void_p(mask.data_ptr()), C.c_void_p(when.data_ptr()), C.c_void_p(ws.data_ptr()), nbytes,
+                  int(nan_aware), int(impl), st, ms.ctypes.data_as(C.c_void_p), route.ctypes.data_as(C.c_void_p)))
+    taken = np.zeros(win.size, dtype=np.uint8)
+    assert lib.smrf_pf_ero_inc_windows(taken.ctypes.data_as(C.c_void_p), int(win.size)) == win.size
+    planes = ws.view(Zd.dtype).view(3, rows, cols)
+    return mask, when, planes, [int(v) for v in route], [int(v) for v in taken]
+
+
+def adopted_radii():
+    """kEroIncAdoptF32 of csrc/ero_inc_adopt.inc: what SMRF_ERO_INC=1 (the default) takes"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    inc = open(os.path.join(root, "neilpy_amd", "csrc", "ero_inc_adopt.inc")).read()
+    adopt = [int(v) for v in re.search(r"kEroIncAdoptF32\[65\] = \{(.*?)\}", inc, re.S).group(1).replace("\n", " ").split(",")]
+    assert len(adopt) == 65
+    return adopt
+
+
+def inc_rule(windows, route, mode, fp32=True):
+    """morph.hip: window i takes the incremental erosion when it runs as two ring passes, the previous window did too,
+    its radius is the previous one's + 1, an instance exists (fp32, 16..64) and, under mode 1, the table adopts the radius"""
+    from neilpy_amd import _lib
+    adopt = adopted_radii()
+    win = [int(v) for v in windows]
+    return [int(mode != 0 and fp32 and i > 0 and route[i] == _lib.ROUTE_TWO_PASS and route[i - 1] == _lib.ROUTE_TWO_PASS and
+                win[i] == win[i - 1] + 1 and 16 <= win[i] <= 64 and (mode == 2 or bool(adopt[win[i]]))) for i in range(len(win))]

@@ -1,12 +1,11 @@
 """The incremental erosion route of progressive_filter (csrc/morph_incero.h) on the GPU: every radius
 16..64 against the ring erosion it replaces (SMRF_ERO_INC=2 against 0) - mask, when_dropped, and the last opened and
 eroded surfaces in the workspace, bit for bit - and which windows are eligible."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from conftest import switch
+from pf_run import run_pf
 
 pytestmark = pytest.mark.gpu
 
@@ -16,32 +15,6 @@ def nz(gpu_device):
     import neilpy_amd
     neilpy_amd.load_library()
     return neilpy_amd
-
-
-def run_pf(Zd, windows, nan_aware=-1, impl=0):
-    """(mask, when, the workspace's three planes, route per window, took the incremental erosion per window)"""
-    import torch
-    from neilpy_amd import _lib
-    lib = _lib.load()
-    rows, cols = Zd.shape
-    win = np.ascontiguousarray(np.asarray(windows, dtype=np.int32))
-    thr = np.ascontiguousarray(.15 * (win * 1.0))
-    sfx = "f32" if Zd.dtype == torch.float32 else "f64"
-    nbytes = lib.smrf_progressive_filter_workspace_bytes(rows, cols, Zd.element_size())
-    ws = torch.zeros(nbytes, dtype=torch.uint8, device=Zd.device)
-    mask = torch.empty((rows, cols), dtype=torch.uint8, device=Zd.device)
-    when = torch.empty((rows, cols), dtype=torch.uint8, device=Zd.device)
-    ms = np.zeros(win.size, dtype=np.float32)
-    route = np.zeros(win.size, dtype=np.int32)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    fn = getattr(lib, "smrf_progressive_filter_timed_" + sfx)
-    _lib.check(fn(C.c_void_p(Zd.data_ptr()), rows, cols, win.ctypes.data_as(C.c_void_p), thr.ctypes.data_as(C.c_void_p),
-                  int(win.size), C.c_void_p(mask.data_ptr()), C.c_void_p(when.data_ptr()), C.c_void_p(ws.data_ptr()), nbytes,
-                  int(nan_aware), int(impl), st, ms.ctypes.data_as(C.c_void_p), route.ctypes.data_as(C.c_void_p)))
-    taken = np.zeros(win.size, dtype=np.uint8)
-    assert lib.smrf_pf_ero_inc_windows(taken.ctypes.data_as(C.c_void_p), int(win.size)) == win.size
-    planes = ws.view(Zd.dtype).view(3, rows, cols)
-    return mask, when, planes, [int(v) for v in route], [int(v) for v in taken]
 
 
 def raster(nz, rows, cols, seed):

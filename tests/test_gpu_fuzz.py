@@ -94,3 +94,73 @@ def test_progressive_filter_random(nz, orc, seed, shape, dtype, windows):
     m, w = nz.progressive_filter(Z, win, .5, .2, return_when_dropped=True)
     m2, w2 = orc.progressive_filter(Z, win, .5, .2, return_when_dropped=True)
     assert np.array_equal(m, m2) and np.array_equal(w, w2)
+
+
+# Large radii, awkward shapes, forced routes (windows from 0..64, half with a consecutive run; rows 1..300, columns 1..700
+# biased to 1, 2, 7, 8, 9, 255..257, 511..513, plus three rasters of 10 or more strips by at most 60 rows; the second half
+# under one drawn combination of the routing switches).  Drawn once from numpy's default_rng(20261016) and kept as a literal,
+# so a failure names its case and replays alone; tools/fuzz_campaign.py draws its `pf` cases from the same space.
+LARGE = [
+    # seed, shape, dtype, windows, switches
+    (300, (8, 390), 'f32', [46, 61, 10, 11, 12, 13, 16], {}),
+    (301, (60, 233), 'f64', [7, 8, 53, 48, 46, 0, 52], {}),
+    (302, (81, 658), 'f32', [25, 21, 27, 9], {}),
+    (303, (8, 273), 'f32', [24, 4, 22, 45, 35, 34, 60], {}),
+    (304, (157, 9), 'f64', [44, 45, 46, 47, 48, 49], {}),
+    (305, (87, 9), 'f64', [61, 62, 63], {}),
+    (306, (9, 210), 'f32', [64, 55, 4, 1, 35, 4, 35], {}),
+    (307, (257, 143), 'f64', [27], {}),
+    (308, (1, 526), 'f32', [20, 21, 22, 23, 24, 25], {}),
+    (309, (257, 8), 'f64', [53, 54, 9, 3, 34, 56, 8], {}),
+    (310, (230, 327), 'f32', [39, 22, 18], {}),
+    (311, (134, 605), 'f32', [61, 38, 44, 19, 45], {}),
+    (312, (39, 4097), 'f64', [39], {}),
+    (313, (1, 257), 'f64', [8], {}),
+    (314, (99, 1), 'f32', [49, 21, 63, 30], {}),
+    (315, (64, 255), 'f64', [41, 6, 61, 24, 52, 24, 7], {}),
+    (316, (1, 201), 'f32', [33, 34], {}),
+    (317, (223, 255), 'f64', [6, 54, 0, 1, 2], {}),
+    (318, (46, 1), 'f32', [4, 31, 10, 48, 12], {}),
+    (319, (255, 91), 'f32', [32, 30, 3, 8, 6, 51, 55], {}),
+    (320, (85, 511), 'f64', [49, 50, 51, 52], {'SMRF_NT': 1, 'SMRF_SEG_RULE': 2, 'SMRF_XCD_REMAP': 0}),
+    (321, (201, 34), 'f64', [15, 16], {'SMRF_FUSED': 0, 'SMRF_CHAIN': 0, 'SMRF_ERO_INC': 0, 'SMRF_RING_SEG': 50, 'SMRF_SEG_RULE': 1}),
+    (322, (7, 141), 'f32', [57], {'SMRF_FUSED': 0, 'SMRF_NT': 1}),
+    (323, (29, 405), 'f64', [16, 43, 0, 62, 52, 56, 30, 51], {'SMRF_RING_DUAL': 1, 'SMRF_SEG_RULE': 2}),
+    (324, (1, 7), 'f32', [42, 43], {'SMRF_FUSED': 2, 'SMRF_NT': 1, 'SMRF_RING_SEG': 50, 'SMRF_XCD_REMAP': 0}),
+    (325, (7, 4353), 'f64', [22, 23], {'SMRF_FUSED': 0, 'SMRF_RING_SEG': 50}),
+    (326, (257, 270), 'f32', [8, 5, 12, 25, 53, 60, 41, 14], {'SMRF_FUSED': 2, 'SMRF_CHAIN': 0, 'SMRF_ERO_INC': 2, 'SMRF_RING_DUAL': 0, 'SMRF_SEG_RULE': 2, 'SMRF_XCD_REMAP': 0}),
+    (327, (155, 370), 'f32', [22, 3, 5, 44, 8, 27, 36], {'SMRF_FUSED': 2, 'SMRF_CHAIN': 0, 'SMRF_RING_DUAL': 0, 'SMRF_NT': 0, 'SMRF_XCD_REMAP': 0}),
+    (328, (7, 1), 'f64', [6, 7, 8], {'SMRF_CHAIN': 0, 'SMRF_ERO_INC': 0, 'SMRF_SEG_RULE': 1, 'SMRF_XCD_REMAP': 0}),
+    (329, (74, 8), 'f64', [57, 16, 17, 18, 19, 20, 14, 30], {'SMRF_FUSED': 2}),
+    (330, (4, 604), 'f32', [50, 46, 59, 6], {'SMRF_RING_DUAL': 1, 'SMRF_RING_SEG': 50, 'SMRF_XCD_REMAP': 0}),
+    (331, (9, 663), 'f64', [0, 42, 3, 47, 54, 53, 44], {'SMRF_ERO_INC': 0, 'SMRF_RING_DUAL': 0, 'SMRF_RING_SEG': 8, 'SMRF_SEG_RULE': 1, 'SMRF_XCD_REMAP': 0}),
+    (332, (122, 699), 'f32', [44, 53, 3, 4, 54], {'SMRF_FUSED': 0, 'SMRF_ERO_INC': 2, 'SMRF_RING_DUAL': 0}),
+    (333, (81, 80), 'f64', [57, 51, 52, 53, 54, 23, 15], {'SMRF_FUSED': 0, 'SMRF_ERO_INC': 0, 'SMRF_NT': 1, 'SMRF_RING_SEG': 50, 'SMRF_XCD_REMAP': 0}),
+    (334, (19, 512), 'f32', [19, 31, 22, 42, 19, 61, 60, 7], {'SMRF_FUSED': 2, 'SMRF_CHAIN': 0, 'SMRF_ERO_INC': 0, 'SMRF_RING_SEG': 136, 'SMRF_SEG_RULE': 1}),
+    (335, (53, 541), 'f32', [9], {'SMRF_FUSED': 2, 'SMRF_ERO_INC': 2, 'SMRF_RING_DUAL': 1, 'SMRF_RING_SEG': 136, 'SMRF_SEG_RULE': 1}),
+    (336, (2, 170), 'f64', [25, 35, 13, 14], {'SMRF_CHAIN': 0, 'SMRF_NT': 1, 'SMRF_SEG_RULE': 1, 'SMRF_XCD_REMAP': 0}),
+    (337, (114, 8), 'f64', [39, 22, 14, 41, 27, 7, 8], {'SMRF_CHAIN': 0, 'SMRF_SEG_RULE': 1}),
+    (338, (28, 2305), 'f32', [7, 51, 9], {'SMRF_CHAIN': 0, 'SMRF_ERO_INC': 2, 'SMRF_RING_SEG': 24}),
+    (339, (257, 199), 'f64', [52, 1], {'SMRF_RING_DUAL': 0, 'SMRF_RING_SEG': 50, 'SMRF_SEG_RULE': 2, 'SMRF_XCD_REMAP': 0}),
+]
+
+
+def large_raster(seed, shape, dtype):
+    rng = np.random.default_rng(seed)
+    return (rng.normal(0, 1, shape).cumsum(0).cumsum(1) * 0.05 + 200 + (rng.random(shape) < .06) * rng.uniform(1, 25, shape)).astype(dtype)
+
+
+@pytest.mark.parametrize("case", LARGE, ids=[str(c[0]) for c in LARGE])
+def test_progressive_filter_random_large_radii(nz, monkeypatch, case):
+    """mask and when_dropped against tests/morph_numpy.py (the period-2n reflect at any radius), bit for bit"""
+    import morph_numpy as mn
+    from conftest import switch
+    seed, shape, dtype, windows, switches = case
+    assert 1 <= len(windows) <= 8 and min(windows) >= 0 and max(windows) <= 64
+    Z = large_raster(seed, shape, np.float32 if dtype == "f32" else np.float64)
+    win = np.asarray(windows)
+    for name, value in switches.items():
+        switch(monkeypatch, name, value)
+    m, w = nz.progressive_filter(Z, win, 1, .15, return_when_dropped=True)
+    m2, w2 = mn.progressive_filter(Z, win, 1, .15, return_when_dropped=True)
+    assert np.array_equal(m, m2) and np.array_equal(w, w2)

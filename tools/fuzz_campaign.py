@@ -12,6 +12,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 ap = argparse.ArgumentParser()
 ap.add_argument("--cases", type=int, default=200)
 ap.add_argument("--seed", type=int, default=1)
@@ -21,6 +22,7 @@ ap.add_argument("--dump", default="", help="with --only on an smrf case: save it
 a = ap.parse_args()
 import neilpy_amd as nz  # noqa: E402
 from oracle import smrf_oracle as orc  # noqa: E402
+import morph_numpy  # noqa: E402  (tests/morph_numpy.py: the fast reference of progressive_filter)
 
 class _Skip(Exception):
     pass
@@ -105,17 +107,26 @@ for k in range(a.cases):
                 else:
                     bad.append((k, kind, dict(info, margin=margin)))
         elif kind == "pf":
-            shape = (int(rng.integers(1, 140)), int(rng.integers(1, 200)))
+            # the space tests/test_gpu_fuzz.py::test_progressive_filter_random_large_radii holds a drawn subset of: any radius
+            # 0..64 on any shape (tests/morph_numpy.py is the period-2n reflect, valid beyond scipy's 4 min(rows, cols))
+            edge = rng.random(2) < .45
+            shape = (int(rng.choice([1, 2, 7, 8, 9, 255, 256, 257])) if edge[0] else int(rng.integers(1, 301)),
+                     int(rng.choice([1, 2, 7, 8, 9, 255, 256, 257, 511, 512, 513])) if edge[1] else int(rng.integers(1, 701)))
+            if rng.random() < .08:                        # 10 or more strips, short
+                shape = (int(rng.integers(1, 61)), int(rng.choice([2305, 2400, 3000, 4097, 4353])))
             dt = rng.choice([np.float32, np.float64])
             Z = (rng.normal(0, 1, shape).cumsum(0).cumsum(1) * .05 + 200 + (rng.random(shape) < .06) * rng.uniform(1, 25, shape)).astype(dt)
-            win = rng.integers(0, 40, size=int(rng.integers(1, 7)))
-            if 4 * min(shape) <= win.max():               # scipy's own reflect bug regime
-                win = np.minimum(win, max(0, 4 * min(shape) - 1))
+            n = int(rng.integers(1, 9))
+            win = rng.integers(0, 65, size=n)
+            if n >= 2 and rng.random() < .5:              # a consecutive run somewhere in the list
+                nrun = int(rng.integers(2, n + 1))
+                at = int(rng.integers(0, n - nrun + 1))
+                win[at:at + nrun] = int(rng.integers(0, 64 - nrun + 2)) + np.arange(nrun)
             cs = float(rng.choice([1, .5, 2]))
             if a.only >= 0 and k != a.only:
                 raise _Skip
             m, w = nz.progressive_filter(Z, win, cs, .15, return_when_dropped=True)
-            m2, w2 = orc.progressive_filter(Z, win, cs, .15, return_when_dropped=True)
+            m2, w2 = morph_numpy.progressive_filter(Z, win, cs, .15, return_when_dropped=True)
             if not (np.array_equal(m, m2) and np.array_equal(w, w2)):
                 bad.append((k, kind, dict(shape=shape, win=win.tolist(), dt=str(dt), diff=int((m != m2).sum()))))
         elif kind == "inpaint":
