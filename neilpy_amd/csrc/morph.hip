@@ -16,22 +16,6 @@ namespace {
 // O(card(disk)) loads per cell - the fallback for radius > SMRF_RING_MAX_RADIUS and the
 // independent on-device cross-check of the ring kernels in the parity tests.
 // ------------------------------------------------------------------------------------------
-// the flag step of one output cell (neilpy.py:1671-1674): sparse, or dense when the planes were not cleared (DiskArgs::dense)
-template <typename T>
-__device__ __forceinline__ void flag_cell(const DiskArgs<T>& a, long long off, T lastval, T val) {
-  const T diff = lastval - val;                            // raster dtype
-  bool hit;                                                // float64 comparison (NumPy 2); fp32: smrf_float_below
-  if constexpr (sizeof(T) == 4) hit = diff > a.thr_lo;
-  else hit = (double)diff > a.thr;
-  if (a.dense) {
-    a.mask[off] = hit ? 1 : 0;
-    if (a.when != nullptr) a.when[off] = hit ? (uint8_t)a.widx : (uint8_t)0;
-  } else if (hit) {
-    a.mask[off] = 1;
-    if (a.when != nullptr) a.when[off] = (uint8_t)a.widx;
-  }
-}
-
 template <typename T, bool DIL>
 __global__ __launch_bounds__(256) void direct_kernel(const DiskArgs<T> a) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63);
@@ -57,7 +41,7 @@ __global__ __launch_bounds__(256) void direct_kernel(const DiskArgs<T> a) {
   if (a.nan_aware && first_nan) best = DIL ? (T)NAN : (T)NAN;
   const long long off = (long long)(y - a.out_row0) * a.ld + x;
   a.out[off] = best;
-  if (a.mask != nullptr) flag_cell(a, off, a.last[off], best);
+  if (a.mask != nullptr) smrf::smrf_flag_cell(a, off, a.last[off], best);
 }
 
 template <typename T>
@@ -68,7 +52,7 @@ __global__ __launch_bounds__(256) void copy_flag_kernel(const DiskArgs<T> a) {  
     const T v = a.in[(long long)(a.out_row0 + yy - a.in_row0) * a.ld + x];
     const long long off = (long long)yy * a.ld + x;
     a.out[off] = v;
-    if (a.mask != nullptr) flag_cell(a, off, a.last[off], v);
+    if (a.mask != nullptr) smrf::smrf_flag_cell(a, off, a.last[off], v);
   }
 }
 

@@ -76,15 +76,8 @@ void fused_open_kernel(const DiskArgs<T> a) {
   T2* const LD = LE + TABLE;                             // dilation stage: same geometry, cells R .. R + TW - 1 filled
 
   const int tid = threadIdx.x;
-  int bx = blockIdx.x, by = blockIdx.y;                  // XCD-aware placement, as ring_kernel
-#if SMRF_RING_XCD_REMAP
-  if ((gridDim.x & 7) == 0) {
-    const int id = blockIdx.y * gridDim.x + blockIdx.x, per = gridDim.x >> 3;
-    const int xcd = id & 7, slot = id >> 3;
-    bx = xcd * per + slot % per;
-    by = slot / per;
-  }
-#endif
+  int bx, by;   // strip counts that are multiples of 8 only; this kernel ignores the SMRF_XCD_REMAP=0 switch (DiskArgs::plain_tiles)
+  smrf_xcd_tile(!SMRF_RING_XCD_REMAP, [] { return false; }, bx, by);
   const int xe0 = bx * TWO - R;                          // first eroded column of the workgroup
   const int x = xe0 + tid;                               // this lane's column (eroded; opened if it is an inner one)
   const bool writes = tid >= R && tid < TW - R && x < a.cols;

@@ -65,21 +65,8 @@ __global__ __launch_bounds__(256) void inc_erode_kernel(const IncEroArgs<T> a) {
   constexpr int N = C::N, DY = C::DY, TW = C::TW, NP = C::NP, ROWS = C::ROWS, W = C::W, NPOS = C::NPOS, NACC = C::NACC, G = C::G;
   __shared__ T2 L[C::LDS_CELLS];
   const int tid = threadIdx.x;
-  int bx = blockIdx.x, by = blockIdx.y;
-  // XCD-aware tile placement, as the ring kernels: neighbouring strips (which share 2 reach halo columns) on one XCD's L2
-  if (a.plain_tiles) {
-  } else if ((gridDim.x & 7) == 0) {
-    const int id = blockIdx.y * gridDim.x + blockIdx.x, per = gridDim.x >> 3;
-    const int xcd = id & 7, slot = id >> 3;
-    bx = xcd * per + slot % per;
-    by = slot / per;
-  } else if (gridDim.x > 8) {
-    const int total = gridDim.x * gridDim.y, id = blockIdx.y * gridDim.x + blockIdx.x;
-    const int xcd = id & 7, slot = id >> 3, q = total >> 3, rem = total & 7;
-    const int t = xcd * q + (xcd < rem ? xcd : rem) + slot;
-    bx = t / (int)gridDim.y;
-    by = t % (int)gridDim.y;
-  }
+  int bx, by;   // neighbouring strips (which share 2 reach halo columns) on one XCD's L2
+  smrf_xcd_tile(a.plain_tiles, [] { return true; }, bx, by);
   const int x0 = bx * TW, x = x0 + tid;
   const int ys = by * a.seg, ye = min(a.rows, ys + a.seg);   // output rows [ys, ye)
   if (ys >= ye) return;

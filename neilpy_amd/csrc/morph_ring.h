@@ -36,27 +36,9 @@
 
 #include "smrf_common.h"
 
-// lookup groups in flight: a third buffer (+16 VGPRs in fp32) only where the kernel sits at 2 waves/SIMD
-// anyway (demand above 168 VGPRs) and the extra registers do not cost a wave
-// lookup groups in flight.  Measured in both rounds: a third group in flight gains nothing at any radius and costs a
-// wave at some (R = 28: 0.873 vs 0.838 ms, gpurun_out/r02/probe_exp2.log) - lookup latency is not what the consume
-// phase waits for.
-#ifndef SMRF_RING_DEPTH
-#define SMRF_RING_DEPTH(need) 2
-#endif
-#ifndef SMRF_RING_BUILD_PRIO
-#define SMRF_RING_BUILD_PRIO 3
-#endif
-#ifndef SMRF_RING_LOOKUP_PRIO
-#define SMRF_RING_LOOKUP_PRIO 1
-#endif
-// columns (= lanes) per workgroup: 256 (shared table, barriers); tuning builds may fix 64 (wave-private table) or 512
-// (fp32 only) with -DSMRF_RING_TW=n
-#ifdef SMRF_RING_TW
-#define SMRF_RING_TW_OF(T, R) SMRF_RING_TW
-#else
-#define SMRF_RING_TW_OF(T, R) ring_tuned_tw<T>(R)
-#endif
+// The compile-time knobs of tuning builds (-DNAME=...); a product build takes every default below.  What earlier rounds
+// settled by measurement is a constant further down (kRingTW, kRingBuildPrio, kRingLookupPrio, RingCfg::D).
+//
 // lookups per pipelined group: 4 for the small disks; 2 or 3 for the large ones, whose ring leaves
 // few registers for lookups in flight (measured per radius: tools/ring_tune.py --variants cur,g2,g3,g6)
 // fp64: per radius where ring_tune.inc says so (kRingGF64, round 5: the register rule below was written for fp32)
@@ -77,7 +59,7 @@
 #define SMRF_RING_NP_MAX 2
 #endif
 #ifndef SMRF_RING_XCD_REMAP
-#define SMRF_RING_XCD_REMAP 1   // XCD-aware tile placement (see ring_kernel)
+#define SMRF_RING_XCD_REMAP 1   // XCD-aware tile placement (smrf_xcd_tile); 0: workgroup (x, y) takes tile (x, y)
 #endif
 #ifndef SMRF_RING_SLOPE_DEFAULT
 #define SMRF_RING_SLOPE_DEFAULT 60  // permille of segment length per residency class (ring_launch_np); SMRF_RING_SLOPE overrides
@@ -100,25 +82,16 @@
 #define SMRF_RING_JCAP(T, R) ring_tuned_jcap<T>(R)
 #endif
 // second half of the ring updated in place (RingCfg::INPLACE): per radius from ring_inpl.inc, or everywhere / nowhere in
-// tuning builds; SLACK: registers added to the kernel's demand estimate (tuning the occupancy step it is built for)
+// tuning builds
 #ifndef SMRF_RING_INPLACE
 #define SMRF_RING_INPLACE(T, R) ring_tuned_inplace<T>(R)
 #endif
-#ifndef SMRF_RING_BASE_PB
-#define SMRF_RING_BASE_PB(T, R) 0   // 0: the default of RingCfg::BASE_PB
-#endif
-#ifndef SMRF_RING_INPLACE_SLACK
-#define SMRF_RING_INPLACE_SLACK 0
-#endif
-// in-place instances from R = 39 up (the 3-wave ones whose register budget is the point; R = 15..17 and 36 measured
-// +-0 ... +2.6 percent with either and keep round 3's first form): smrf_rare, and the turn-back of the ring as asm moves
-// in-place instances: lookups per group / groups in flight (0: as the shifting ring, SMRF_RING_G / SMRF_RING_DEPTH)
+// in-place instances: lookups per group (0: as the shifting ring, SMRF_RING_G)
 #ifndef SMRF_RING_INPLACE_G
 #define SMRF_RING_INPLACE_G(T, R) ring_tuned_inplace_g<T>(R)
 #endif
-#ifndef SMRF_RING_INPLACE_D
-#define SMRF_RING_INPLACE_D(T, R) 0
-#endif
+// in-place instances from R = 39 up (the 3-wave ones whose register budget is the point; R = 15..17 and 36 measured
+// +-0 ... +2.6 percent with either and keep round 3's first form): smrf_rare, and the turn-back of the ring as asm moves
 #ifndef SMRF_RING_RARE_OPAQUE
 #define SMRF_RING_RARE_OPAQUE(T, R) ((R) >= 39 || ring_tuned_inplace_occ<T>(R) == 4)
 #endif
@@ -139,11 +112,6 @@
 #ifndef SMRF_RING_NP_MAX_OF
 #define SMRF_RING_NP_MAX_OF(T, R) ring_tuned_np_max<T>(R)
 #endif
-#ifndef SMRF_FORCE_OCC
-#define SMRF_OCC_OVERRIDE(...) __VA_ARGS__
-#else
-#define SMRF_OCC_OVERRIDE(...) SMRF_FORCE_OCC
-#endif
 
 // tools/isa_budget.py builds single instances with -DSMRF_ISA_MARK: comment lines in the assembly that name the phase
 // the instructions after them belong to (the min / max and LDS instructions are volatile asm and keep their order against
@@ -155,6 +123,15 @@
 #endif
 
 namespace smrf {
+
+// columns (= lanes) per workgroup: one table shared by four waves, barriers between the phases.  512-column workgroups, one
+// per CU, measured within +-1 % of 256 at R >= 39 and 20-25 % slower below (round 2, probe_tw512).  TW stays a
+// template parameter of the kernels; this is the one value it is instantiated with.
+constexpr int kRingTW = 256;
+// s_setprio levels.  Build phases: they end in barriers the whole workgroup waits at, so a wave in them wins the issue
+// arbitration against the SIMD's other wave (ring_build_consume).  Lookup half of a pair: see ring_consume; levels 1 and 2
+// measured equal, 3 (= the build phases' level) gives the gain back.
+constexpr int kRingBuildPrio = 3, kRingLookupPrio = 1;
 
 // one step down the occupancy ladder the kernels are built for (waves per SIMD)
 constexpr int ring_occ_drop(int occ, int steps) {
@@ -180,10 +157,6 @@ template <typename T> constexpr int ring_tuned_jcap(int r) {
   if (sizeof(T) != 4 || r < 15 || r > 58) return 3;
   return (r == 29 || r == 31 || r == 50) ? 3 : 2;
 }
-
-// columns per workgroup per radius: 256 everywhere (512-column workgroups, one per CU, measured within +-1 % of 256 at
-// R >= 39 and 20-25 % slower below: gpurun_out/r02/probe_tw512.log)
-template <typename T> constexpr int ring_tuned_tw(int) { return 256; }
 
 constexpr int clog2(int v) {  // floor(log2(v)), v >= 1
   int l = 0;
@@ -476,10 +449,13 @@ struct RingCfg {
                                                                      : SMRF_RING_G_OF(T, R, E * (2 * R + 2 * S::K));   // window lookups per pipelined group
   static constexpr int NG = (S::K - 1 + G - 1) / G;      // groups for k = 1..K-1
   static constexpr int gsize(int g) { int n = S::K - 1 - g * G; return n < 0 ? 0 : (n > G ? G : n); }
-  static constexpr int BASE_PB = SMRF_RING_BASE_PB(T, R) > 0 ? SMRF_RING_BASE_PB(T, R) : INPLACE ? 1 : 8;   // row pairs per round trip of the base-level build (in-place kernels are built for registers)
-  static constexpr int NEED_BASE = INPLACE ? E * (2 * R + 2 * (G + 2) + 3 + 20 + 4 * G) + 16 + SMRF_RING_INPLACE_SLACK
-                                           : E * (2 * R + 2 * S::K + 20 + 4 * G) + 16;   // measured VGPR demand at D = 2
-  static constexpr int D = INPLACE && SMRF_RING_INPLACE_D(T, R) > 0 ? SMRF_RING_INPLACE_D(T, R) : SMRF_RING_DEPTH(NEED_BASE);   // lookup groups kept in flight
+  static constexpr int BASE_PB = INPLACE ? 1 : 8;        // row pairs per round trip of the base-level build (in-place kernels are built for registers)
+  // lookup groups kept in flight.  Measured in two rounds: a third group (+16 VGPRs in fp32) gains nothing at any radius
+  // and costs a wave at some (R = 28: 0.873 vs 0.838 ms, round 2, probe_exp2) - lookup latency is not what the
+  // consume phase waits for.
+  static constexpr int D = 2;
+  static constexpr int NEED = INPLACE ? E * (2 * R + 2 * (G + 2) + 3 + 20 + 4 * G) + 16
+                                      : E * (2 * R + 2 * S::K + 20 + 4 * G) + 16;   // measured VGPR demand
   static constexpr int greads(int g) {                   // LDS reads of lookup group g
     int n = 0;
     for (int k = 1 + g * G; k < 1 + (g + 1) * G && k < S::K; ++k) n += INC ? 2 * inc_n(k) : nreads(S::wk(k));
@@ -501,7 +477,6 @@ struct RingCfg {
     return true;
   }
   static constexpr bool SLOT_DELAY = (FUSE_MODE & 2) != 0;   // a group's ring slots updated after the NEXT group's window steps
-  static constexpr int NEED = NEED_BASE + (D - 2) * 4 * G * E;
   static constexpr int OCC_EST = NEED <= 64 ? 8 : NEED <= 96 ? 5 : NEED <= 128 ? 4 : NEED <= 168 ? 3 : NEED <= 264 ? 2 : 1;
   static constexpr int OCC_REG = INPLACE && SMRF_RING_INPLACE_OCC(T, R) > 0 ? SMRF_RING_INPLACE_OCC(T, R)
                                                                           : ring_occ_drop(OCC_EST, SMRF_RING_OCC_DROP_OF(T, R));
@@ -535,7 +510,7 @@ constexpr int ring_np() {
   if constexpr (mx >= 2) if (RingCfg<T, R, TW, 2>::WG_LDS >= want) return 2;
   return 1;
 }
-#define SMRF_RING_NP(T, R) ring_np<T, R, SMRF_RING_TW_OF(T, R)>()
+#define SMRF_RING_NP(T, R) ring_np<T, R, kRingTW>()
 
 
 // Buffer addressing (SMRF_RING_BUF): the common-case loads and stores of the ring kernel as buffer instructions - a
@@ -566,18 +541,12 @@ using smrf_rsrc_t = __amdgpu_buffer_rsrc_t;
 __device__ __forceinline__ smrf_rsrc_t smrf_make_rsrc(const void* p) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, -1, 0x00020000);
 }
-template <bool NT = false>
 __device__ __forceinline__ float smrf_buf_load(smrf_rsrc_t r, unsigned voff, unsigned soff, float) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, NT ? 2 : 0));
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, 0));
 }
-template <bool NT = false>
 __device__ __forceinline__ double smrf_buf_load(smrf_rsrc_t r, unsigned voff, unsigned soff, double) {
-  return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, (int)soff, NT ? 2 : 0));
+  return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, (int)soff, 0));
 }
-// `last` of the flag step in the ring dilation: read once per launch, never again - a streaming load (SMRF_NT_LAST)
-#ifndef SMRF_NT_LAST
-#define SMRF_NT_LAST 0
-#endif
 template <bool NT>
 __device__ __forceinline__ void smrf_buf_store(smrf_rsrc_t r, unsigned voff, unsigned soff, float v) {
   __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)voff, (int)soff, NT ? 2 : 0);
@@ -906,6 +875,118 @@ __device__ __forceinline__ void ring_upper_halo(typename Vec2<T>::type* const L,
   }
 }
 
+// The lookup pipeline of one row pair, shared by ring_consume and ring_consume_inplace: the K distinct window minima of
+// rows A and B (ra, rb; width 0 = the cell itself is the caller's) in lookup groups of G widths, D groups in flight.
+// issue<GI>() puts group GI's LDS reads in flight, reduce<GI>() - after the caller's counted wait - folds them into
+// ra / rb[1 + GI * G ...]: with RingCfg::INC each width grown from the one before it (as one asm statement per group where
+// RingCfg::fused_red says so), otherwise two or three reads of the width's own table level.  The arrays are the caller's
+// locals, held here by reference: so they compile to the very registers they had when issue and reduce were lambdas of the
+// two consume functions; as members of one object they did not (same instructions, other register numbers).
+template <typename T, int R, bool DIL, int TW, int NP>
+struct RingLookups {
+  using C = RingCfg<T, R, TW, NP>;
+  using S = typename C::S;
+  using T2 = typename Vec2<T>::type;
+  static constexpr int K = S::K, WP = C::WP, G = C::G, D = C::D;
+  const unsigned q;                                      // this lane's cell of the pair, level 0 (LDS byte address)
+  // INC reads level 0 as well: this batch's copy of it
+  // (addressed from the row's first staged cell: ds_read offsets are unsigned)
+  const unsigned q0;
+  T (&ra)[K], (&rb)[K];                                  // window results of row A / row B per width
+  // D lookup groups in flight (tc: third read of the widest widths; INC: tc, td second read per side; te, tf third read per
+  // side: a first step of 9..11 cells at level 2)
+  T2 (&ta)[D][G], (&tb)[D][G], (&tc)[D][G], (&td)[D][G], (&te)[D][G], (&tf)[D][G];
+  static __device__ __forceinline__ unsigned level0(unsigned q, int par) {
+    return q + (unsigned)par * (unsigned)(WP * sizeof(T2)) - (unsigned)(R * sizeof(T2));
+  }
+  template <int GI>
+  __device__ __forceinline__ void issue() {
+    [&]<int... I>(std::integer_sequence<int, I...>) {
+      (([&] {
+         constexpr int k = 1 + GI * G + I;
+         if constexpr (k < K && C::INC) {
+           constexpr int w = S::wk(k);
+           constexpr int j = C::inc_lev(k);
+           static_assert(C::stored(j), "step level not built");
+           static_assert(C::inc_n(k) <= 3, "width step longer than three table entries");
+           constexpr int base = j == 0 ? R : C::slot_of(j) * WP;
+           const unsigned qq = j == 0 ? q0 : q;
+           ta[GI % D][I] = lds_read2<(base - w) * (int)sizeof(T2)>(qq, T());
+           tb[GI % D][I] = lds_read2<(base + w - (1 << j) + 1) * (int)sizeof(T2)>(qq, T());
+           if constexpr (C::inc_n(k) >= 2) {
+             tc[GI % D][I] = lds_read2<(base - w + (1 << j)) * (int)sizeof(T2)>(qq, T());
+             td[GI % D][I] = lds_read2<(base + w - (2 << j) + 1) * (int)sizeof(T2)>(qq, T());
+           }
+           if constexpr (C::inc_n(k) == 3) {
+             te[GI % D][I] = lds_read2<(base - w + (2 << j)) * (int)sizeof(T2)>(qq, T());
+             tf[GI % D][I] = lds_read2<(base + w - (3 << j) + 1) * (int)sizeof(T2)>(qq, T());
+           }
+         } else if constexpr (k < K) {
+           constexpr int w = S::wk(k);
+           constexpr int j = C::lev(w);
+           constexpr int base = C::slot_of(j) * WP;
+           static_assert(C::stored(j), "lookup level not built");
+           ta[GI % D][I] = lds_read2<(base - w) * (int)sizeof(T2)>(q, T());
+           tb[GI % D][I] = lds_read2<(base + w - (1 << j) + 1) * (int)sizeof(T2)>(q, T());
+           if constexpr (C::nreads(w) == 3)              // window longer than two entries of the top level: one in between
+             tc[GI % D][I] = lds_read2<(base - w + (1 << j)) * (int)sizeof(T2)>(q, T());
+         }
+       }()), ...);
+    }(std::make_integer_sequence<int, G>{});
+  }
+  template <int GI>
+  __device__ __forceinline__ void reduce() {
+    if constexpr (C::fused_red(GI)) {
+      constexpr int k0 = 1 + GI * G, n = C::gsize(GI), b = GI % D;
+      constexpr int i2 = G > 2 ? 2 : 0, i3 = G > 3 ? 3 : 0;
+      float x0, y0, x1, y1;
+      if constexpr (n == 2) {
+        red_chain<DIL>(ra[k0 - 1], rb[k0 - 1], x0, y0, ta[b][0].x, ta[b][0].y, tb[b][0].x, tb[b][0].y, x1, y1, ta[b][1].x, ta[b][1].y,
+                       tb[b][1].x, tb[b][1].y);
+      } else if constexpr (n == 3) {
+        float x2, y2;
+        red_chain<DIL>(ra[k0 - 1], rb[k0 - 1], x0, y0, ta[b][0].x, ta[b][0].y, tb[b][0].x, tb[b][0].y, x1, y1, ta[b][1].x, ta[b][1].y,
+                       tb[b][1].x, tb[b][1].y, x2, y2, ta[b][i2].x, ta[b][i2].y, tb[b][i2].x, tb[b][i2].y);
+        ra[k0 + 2] = x2; rb[k0 + 2] = y2;
+      } else {
+        float x2, y2, x3, y3;
+        red_chain<DIL>(ra[k0 - 1], rb[k0 - 1], x0, y0, ta[b][0].x, ta[b][0].y, tb[b][0].x, tb[b][0].y, x1, y1, ta[b][1].x, ta[b][1].y,
+                       tb[b][1].x, tb[b][1].y, x2, y2, ta[b][i2].x, ta[b][i2].y, tb[b][i2].x, tb[b][i2].y, x3, y3, ta[b][i3].x,
+                       ta[b][i3].y, tb[b][i3].x, tb[b][i3].y);
+        ra[k0 + 2] = x2; rb[k0 + 2] = y2; ra[k0 + 3] = x3; rb[k0 + 3] = y3;
+      }
+      ra[k0] = x0; rb[k0] = y0; ra[k0 + 1] = x1; rb[k0 + 1] = y1;
+    } else
+    [&]<int... I>(std::integer_sequence<int, I...>) {
+      (([&] {
+         constexpr int k = 1 + GI * G + I;
+         if constexpr (k < K && C::INC) {
+           T a = op3<DIL>(ra[k - 1], ta[GI % D][I].x, tb[GI % D][I].x);
+           T b = op3<DIL>(rb[k - 1], ta[GI % D][I].y, tb[GI % D][I].y);
+           if constexpr (C::inc_n(k) >= 2) {
+             a = op3<DIL>(a, tc[GI % D][I].x, td[GI % D][I].x);
+             b = op3<DIL>(b, tc[GI % D][I].y, td[GI % D][I].y);
+           }
+           if constexpr (C::inc_n(k) == 3) {
+             a = op3<DIL>(a, te[GI % D][I].x, tf[GI % D][I].x);
+             b = op3<DIL>(b, te[GI % D][I].y, tf[GI % D][I].y);
+           }
+           ra[k] = a;
+           rb[k] = b;
+         } else if constexpr (k < K) {
+           if constexpr (C::nreads(S::wk(k)) == 3) {
+             ra[k] = op3<DIL>(ta[GI % D][I].x, tc[GI % D][I].x, tb[GI % D][I].x);
+             rb[k] = op3<DIL>(ta[GI % D][I].y, tc[GI % D][I].y, tb[GI % D][I].y);
+           } else {
+             ra[k] = op2<DIL>(ta[GI % D][I].x, tb[GI % D][I].x);
+             rb[k] = op2<DIL>(ta[GI % D][I].y, tb[GI % D][I].y);
+           }
+         }
+       }()), ...);
+    }(std::make_integer_sequence<int, G>{});
+  }
+};
+
 template <typename T, int R, bool DIL, int TW, int NP>
 __device__ __forceinline__ void ring_consume_inplace(typename Vec2<T>::type* const L, const int par, const int tid,
                                                      T (&acc)[2 * R], T (&outv)[2 * NP]);
@@ -916,6 +997,7 @@ __device__ __forceinline__ void ring_consume(typename Vec2<T>::type* const L, co
   using C = RingCfg<T, R, TW, NP>;
   using S = typename C::S;
   using T2 = typename Vec2<T>::type;
+  using LK = RingLookups<T, R, DIL, TW, NP>;
   if constexpr (C::INPLACE) {
     ring_consume_inplace<T, R, DIL, TW, NP>(L, par, tid, acc, outv);
     return;
@@ -938,97 +1020,10 @@ __device__ __forceinline__ void ring_consume(typename Vec2<T>::type* const L, co
     // half: of the SIMD's two or three waves, the one that can put reads in flight goes first and the other fills the
     // gaps with its min3 stretch.  Measured -4...-8 % at every radius from 20 up (gpurun_out/r02/probe_prio2.log);
     // levels 1 and 2 are equal, 3 (= the build phases' level) gives the gain back.
-    __builtin_amdgcn_s_setprio(SMRF_RING_LOOKUP_PRIO);
-    T ra[K], rb[K];                                      // window results of row A / row B per width
-    T2 ta[D][G], tb[D][G], tc[D][G], td[D][G];          // D lookup groups in flight (tc: third read of the widest widths; INC: tc, td second read per side)
-    T2 te[D][G], tf[D][G];                               // INC: third read per side (a first step of 9..11 cells at level 2)
-    // INC reads level 0 as well: this batch's copy of it
-    // (addressed from the row's first staged cell: ds_read offsets are unsigned)
-    const unsigned q0 = q + (unsigned)par * (unsigned)(WP * sizeof(T2)) - (unsigned)(R * sizeof(T2));
-    auto issue = [&]<int GI>(std::integral_constant<int, GI>) {
-      [&]<int... I>(std::integer_sequence<int, I...>) {
-        (([&] {
-           constexpr int k = 1 + GI * G + I;
-           if constexpr (k < K && C::INC) {
-             constexpr int w = S::wk(k);
-             constexpr int j = C::inc_lev(k);
-             static_assert(C::stored(j), "step level not built");
-             static_assert(C::inc_n(k) <= 3, "width step longer than three table entries");
-             constexpr int base = j == 0 ? R : C::slot_of(j) * WP;
-             const unsigned qq = j == 0 ? q0 : q;
-             ta[GI % D][I] = lds_read2<(base - w) * (int)sizeof(T2)>(qq, T());
-             tb[GI % D][I] = lds_read2<(base + w - (1 << j) + 1) * (int)sizeof(T2)>(qq, T());
-             if constexpr (C::inc_n(k) >= 2) {
-               tc[GI % D][I] = lds_read2<(base - w + (1 << j)) * (int)sizeof(T2)>(qq, T());
-               td[GI % D][I] = lds_read2<(base + w - (2 << j) + 1) * (int)sizeof(T2)>(qq, T());
-             }
-             if constexpr (C::inc_n(k) == 3) {
-               te[GI % D][I] = lds_read2<(base - w + (2 << j)) * (int)sizeof(T2)>(qq, T());
-               tf[GI % D][I] = lds_read2<(base + w - (3 << j) + 1) * (int)sizeof(T2)>(qq, T());
-             }
-           } else if constexpr (k < K) {
-             constexpr int w = S::wk(k);
-             constexpr int j = C::lev(w);
-             constexpr int base = C::slot_of(j) * WP;
-             static_assert(C::stored(j), "lookup level not built");
-             ta[GI % D][I] = lds_read2<(base - w) * (int)sizeof(T2)>(q, T());
-             tb[GI % D][I] = lds_read2<(base + w - (1 << j) + 1) * (int)sizeof(T2)>(q, T());
-             if constexpr (C::nreads(w) == 3)              // window longer than two entries of the top level: one in between
-               tc[GI % D][I] = lds_read2<(base - w + (1 << j)) * (int)sizeof(T2)>(q, T());
-           }
-         }()), ...);
-      }(std::make_integer_sequence<int, G>{});
-    };
-    auto reduce = [&]<int GI>(std::integral_constant<int, GI>) {
-      if constexpr (C::fused_red(GI)) {
-        constexpr int k0 = 1 + GI * G, n = C::gsize(GI), b = GI % D;
-        constexpr int i2 = G > 2 ? 2 : 0, i3 = G > 3 ? 3 : 0;
-        float x0, y0, x1, y1;
-        if constexpr (n == 2) {
-          red_chain<DIL>(ra[k0 - 1], rb[k0 - 1], x0, y0, ta[b][0].x, ta[b][0].y, tb[b][0].x, tb[b][0].y, x1, y1, ta[b][1].x, ta[b][1].y,
-                         tb[b][1].x, tb[b][1].y);
-        } else if constexpr (n == 3) {
-          float x2, y2;
-          red_chain<DIL>(ra[k0 - 1], rb[k0 - 1], x0, y0, ta[b][0].x, ta[b][0].y, tb[b][0].x, tb[b][0].y, x1, y1, ta[b][1].x, ta[b][1].y,
-                         tb[b][1].x, tb[b][1].y, x2, y2, ta[b][i2].x, ta[b][i2].y, tb[b][i2].x, tb[b][i2].y);
-          ra[k0 + 2] = x2; rb[k0 + 2] = y2;
-        } else {
-          float x2, y2, x3, y3;
-          red_chain<DIL>(ra[k0 - 1], rb[k0 - 1], x0, y0, ta[b][0].x, ta[b][0].y, tb[b][0].x, tb[b][0].y, x1, y1, ta[b][1].x, ta[b][1].y,
-                         tb[b][1].x, tb[b][1].y, x2, y2, ta[b][i2].x, ta[b][i2].y, tb[b][i2].x, tb[b][i2].y, x3, y3, ta[b][i3].x,
-                         ta[b][i3].y, tb[b][i3].x, tb[b][i3].y);
-          ra[k0 + 2] = x2; rb[k0 + 2] = y2; ra[k0 + 3] = x3; rb[k0 + 3] = y3;
-        }
-        ra[k0] = x0; rb[k0] = y0; ra[k0 + 1] = x1; rb[k0 + 1] = y1;
-      } else
-      [&]<int... I>(std::integer_sequence<int, I...>) {
-        (([&] {
-           constexpr int k = 1 + GI * G + I;
-           if constexpr (k < K && C::INC) {
-             T a = op3<DIL>(ra[k - 1], ta[GI % D][I].x, tb[GI % D][I].x);
-             T b = op3<DIL>(rb[k - 1], ta[GI % D][I].y, tb[GI % D][I].y);
-             if constexpr (C::inc_n(k) >= 2) {
-               a = op3<DIL>(a, tc[GI % D][I].x, td[GI % D][I].x);
-               b = op3<DIL>(b, tc[GI % D][I].y, td[GI % D][I].y);
-             }
-             if constexpr (C::inc_n(k) == 3) {
-               a = op3<DIL>(a, te[GI % D][I].x, tf[GI % D][I].x);
-               b = op3<DIL>(b, te[GI % D][I].y, tf[GI % D][I].y);
-             }
-             ra[k] = a;
-             rb[k] = b;
-           } else if constexpr (k < K) {
-             if constexpr (C::nreads(S::wk(k)) == 3) {
-               ra[k] = op3<DIL>(ta[GI % D][I].x, tc[GI % D][I].x, tb[GI % D][I].x);
-               rb[k] = op3<DIL>(ta[GI % D][I].y, tc[GI % D][I].y, tb[GI % D][I].y);
-             } else {
-               ra[k] = op2<DIL>(ta[GI % D][I].x, tb[GI % D][I].x);
-               rb[k] = op2<DIL>(ta[GI % D][I].y, tb[GI % D][I].y);
-             }
-           }
-         }()), ...);
-      }(std::make_integer_sequence<int, G>{});
-    };
+    __builtin_amdgcn_s_setprio(kRingLookupPrio);
+    T ra[K], rb[K];
+    T2 ta[D][G], tb[D][G], tc[D][G], td[D][G], te[D][G], tf[D][G];
+    LK lk{q, LK::level0(q, par), ra, rb, ta, tb, tc, td, te, tf};
     auto slots = [&]<int GI>(std::integral_constant<int, GI>) {   // ring slots released by group GI
       [&]<int... Sl>(std::integer_sequence<int, Sl...>) {
         (([&] {
@@ -1041,7 +1036,7 @@ __device__ __forceinline__ void ring_consume(typename Vec2<T>::type* const L, co
     };
 
     [&]<int... GI>(std::integer_sequence<int, GI...>) {   // prologue: the first D-1 groups
-      (([&] { if constexpr (GI < NG) issue(std::integral_constant<int, GI>{}); }()), ...);
+      (([&] { if constexpr (GI < NG) lk.template issue<GI>(); }()), ...);
     }(std::make_integer_sequence<int, D - 1>{});
     ra[0] = own[p].x;
     rb[0] = own[p].y;
@@ -1050,9 +1045,9 @@ __device__ __forceinline__ void ring_consume(typename Vec2<T>::type* const L, co
     constexpr bool SD = C::SLOT_DELAY && NG >= 2;          // slots one group late (RingCfg::SLOT_DELAY)
     [&]<int... GI>(std::integer_sequence<int, GI...>) {
       (([&] {
-         if constexpr (GI + D - 1 < NG) issue(std::integral_constant<int, GI + D - 1>{});
+         if constexpr (GI + D - 1 < NG) lk.template issue<GI + D - 1>();
          lds_wait<C::inflight_after(GI), (C::FUSE_MODE != 0)>();   // reads of the groups issued after group GI
-         reduce(std::integral_constant<int, GI>{});
+         lk.template reduce<GI>();
          constexpr int GS = SD ? GI - 1 : GI;             // the group whose slots are updated here
          if constexpr (GS == 0) {
            if constexpr (R >= 2) outv[2 * p + 1] = op3<DIL>(acc[1], ra[KR1], rb[0]);
@@ -1087,6 +1082,7 @@ __device__ __forceinline__ void ring_consume_inplace(typename Vec2<T>::type* con
   using C = RingCfg<T, R, TW, NP>;
   using S = typename C::S;
   using T2 = typename Vec2<T>::type;
+  using LK = RingLookups<T, R, DIL, TW, NP>;
   static_assert(C::INC && R >= 4, "in-place ring: incremental widths, R >= 4");
   constexpr int K = S::K, WP = C::WP, G = C::G, NG = C::NG, NLEV = C::NLEV, D = C::D;
   constexpr int KR1 = S::kidx(R - 1);
@@ -1100,77 +1096,10 @@ __device__ __forceinline__ void ring_consume_inplace(typename Vec2<T>::type* con
   lds_wait<0>();
   auto pair_body = [&]<int P>(std::integral_constant<int, P>) {
     const unsigned q = lds_q + P * NLEV * WP * (unsigned)sizeof(T2);
-    __builtin_amdgcn_s_setprio(SMRF_RING_LOOKUP_PRIO);
+    __builtin_amdgcn_s_setprio(kRingLookupPrio);
     T ra[K], rb[K];
     T2 ta[D][G], tb[D][G], tc[D][G], td[D][G], te[D][G], tf[D][G];
-    const unsigned q0 = q + (unsigned)par * (unsigned)(WP * sizeof(T2)) - (unsigned)(R * sizeof(T2));
-    auto issue = [&]<int GI>(std::integral_constant<int, GI>) {
-      [&]<int... I>(std::integer_sequence<int, I...>) {
-        (([&] {
-           constexpr int k = 1 + GI * G + I;
-           if constexpr (k < K) {
-             constexpr int w = S::wk(k);
-             constexpr int j = C::inc_lev(k);
-             static_assert(C::stored(j), "step level not built");
-             static_assert(C::inc_n(k) <= 3, "width step longer than three table entries");
-             constexpr int base = j == 0 ? R : C::slot_of(j) * WP;
-             const unsigned qq = j == 0 ? q0 : q;
-             ta[GI % D][I] = lds_read2<(base - w) * (int)sizeof(T2)>(qq, T());
-             tb[GI % D][I] = lds_read2<(base + w - (1 << j) + 1) * (int)sizeof(T2)>(qq, T());
-             if constexpr (C::inc_n(k) >= 2) {
-               tc[GI % D][I] = lds_read2<(base - w + (1 << j)) * (int)sizeof(T2)>(qq, T());
-               td[GI % D][I] = lds_read2<(base + w - (2 << j) + 1) * (int)sizeof(T2)>(qq, T());
-             }
-             if constexpr (C::inc_n(k) == 3) {
-               te[GI % D][I] = lds_read2<(base - w + (2 << j)) * (int)sizeof(T2)>(qq, T());
-               tf[GI % D][I] = lds_read2<(base + w - (3 << j) + 1) * (int)sizeof(T2)>(qq, T());
-             }
-           }
-         }()), ...);
-      }(std::make_integer_sequence<int, G>{});
-    };
-    auto reduce = [&]<int GI>(std::integral_constant<int, GI>) {
-      if constexpr (C::fused_red(GI)) {
-        constexpr int k0 = 1 + GI * G, n = C::gsize(GI), b = GI % D;
-        constexpr int i2 = G > 2 ? 2 : 0, i3 = G > 3 ? 3 : 0;
-        float x0, y0, x1, y1;
-        if constexpr (n == 2) {
-          red_chain<DIL>(ra[k0 - 1], rb[k0 - 1], x0, y0, ta[b][0].x, ta[b][0].y, tb[b][0].x, tb[b][0].y, x1, y1, ta[b][1].x, ta[b][1].y,
-                         tb[b][1].x, tb[b][1].y);
-        } else if constexpr (n == 3) {
-          float x2, y2;
-          red_chain<DIL>(ra[k0 - 1], rb[k0 - 1], x0, y0, ta[b][0].x, ta[b][0].y, tb[b][0].x, tb[b][0].y, x1, y1, ta[b][1].x, ta[b][1].y,
-                         tb[b][1].x, tb[b][1].y, x2, y2, ta[b][i2].x, ta[b][i2].y, tb[b][i2].x, tb[b][i2].y);
-          ra[k0 + 2] = x2; rb[k0 + 2] = y2;
-        } else {
-          float x2, y2, x3, y3;
-          red_chain<DIL>(ra[k0 - 1], rb[k0 - 1], x0, y0, ta[b][0].x, ta[b][0].y, tb[b][0].x, tb[b][0].y, x1, y1, ta[b][1].x, ta[b][1].y,
-                         tb[b][1].x, tb[b][1].y, x2, y2, ta[b][i2].x, ta[b][i2].y, tb[b][i2].x, tb[b][i2].y, x3, y3, ta[b][i3].x,
-                         ta[b][i3].y, tb[b][i3].x, tb[b][i3].y);
-          ra[k0 + 2] = x2; rb[k0 + 2] = y2; ra[k0 + 3] = x3; rb[k0 + 3] = y3;
-        }
-        ra[k0] = x0; rb[k0] = y0; ra[k0 + 1] = x1; rb[k0 + 1] = y1;
-      } else
-      [&]<int... I>(std::integer_sequence<int, I...>) {
-        (([&] {
-           constexpr int k = 1 + GI * G + I;
-           if constexpr (k < K) {
-             T a = op3<DIL>(ra[k - 1], ta[GI % D][I].x, tb[GI % D][I].x);
-             T b = op3<DIL>(rb[k - 1], ta[GI % D][I].y, tb[GI % D][I].y);
-             if constexpr (C::inc_n(k) >= 2) {
-               a = op3<DIL>(a, tc[GI % D][I].x, td[GI % D][I].x);
-               b = op3<DIL>(b, tc[GI % D][I].y, td[GI % D][I].y);
-             }
-             if constexpr (C::inc_n(k) == 3) {
-               a = op3<DIL>(a, te[GI % D][I].x, tf[GI % D][I].x);
-               b = op3<DIL>(b, te[GI % D][I].y, tf[GI % D][I].y);
-             }
-             ra[k] = a;
-             rb[k] = b;
-           }
-         }()), ...);
-      }(std::make_integer_sequence<int, G>{});
-    };
+    LK lk{q, LK::level0(q, par), ra, rb, ta, tb, tc, td, te, tf};
     // (k - 1) / G: the lookup group that completes width index k >= 1
     auto slots = [&]<int GI>(std::integral_constant<int, GI>) {
       // first half, s = 0 .. R-2, ascending (F[R-3], F[R-2] take their shifted-in value from B[0], B[1])
@@ -1196,7 +1125,7 @@ __device__ __forceinline__ void ring_consume_inplace(typename Vec2<T>::type* con
       }(std::make_integer_sequence<int, R - 1>{});
     };
     [&]<int... GI>(std::integer_sequence<int, GI...>) {   // prologue: the first D-1 groups
-      (([&] { if constexpr (GI < NG) issue(std::integral_constant<int, GI>{}); }()), ...);
+      (([&] { if constexpr (GI < NG) lk.template issue<GI>(); }()), ...);
     }(std::make_integer_sequence<int, D - 1>{});
     ra[0] = own[P].x;
     rb[0] = own[P].y;
@@ -1204,9 +1133,9 @@ __device__ __forceinline__ void ring_consume_inplace(typename Vec2<T>::type* con
     constexpr bool SD = C::SLOT_DELAY && NG >= 2;          // slots one group late (RingCfg::SLOT_DELAY)
     [&]<int... GI>(std::integer_sequence<int, GI...>) {
       (([&] {
-         if constexpr (GI + D - 1 < NG) issue(std::integral_constant<int, GI + D - 1>{});
+         if constexpr (GI + D - 1 < NG) lk.template issue<GI + D - 1>();
          lds_wait<C::inflight_after(GI), (C::FUSE_MODE != 0)>();
-         reduce(std::integral_constant<int, GI>{});
+         lk.template reduce<GI>();
          constexpr int GS = SD ? GI - 1 : GI;             // the group whose slots are updated here
          if constexpr (GS == (KR1 - 1) / G) outv[2 * P + 1] = op3<DIL>(acc[1], ra[KR1], rb[0]);   // before F[1] is overwritten
          if constexpr (!SD && GI == NG - 1) __builtin_amdgcn_s_setprio(0);
@@ -1255,21 +1184,19 @@ __device__ __forceinline__ void ring_build_consume(typename Vec2<T>::type* const
                                                    T (&acc)[2 * R], T (&outv)[2 * NP], Sync&& phase_sync) {
   // the build phases end in barriers the whole workgroup waits at: let a wave in them win the issue arbitration
   // against the SIMD's other wave (which is usually consuming); measured -3...-5.5 % at every radius >= 8
-  __builtin_amdgcn_s_setprio(SMRF_RING_BUILD_PRIO);
-#ifndef SMRF_RING_DBG_NOBUILD   // (timing experiment only, wrong results: what the table build costs)
+  __builtin_amdgcn_s_setprio(kRingBuildPrio);
   ring_base<T, R, DIL, TW, NP, NPB, OFF>(L, par, tid, has_last, v);
   phase_sync();
   if constexpr (RingCfg<T, R, TW, NP>::J > RingCfg<T, R, TW, NP>::JB) {
     ring_upper<T, R, DIL, TW, NP, NPB, OFF>(L, tid, has_last, v);
     phase_sync();
   }
-#endif
   __builtin_amdgcn_s_setprio(0);
   ring_consume<T, R, DIL, TW, NP>(L, par, tid, acc, outv);
 }
 
 template <typename T, int R, bool DIL, int TW, int NP>
-__global__ __launch_bounds__(TW, (SMRF_OCC_OVERRIDE(TW > 256 ? (RingCfg<T, R, TW, NP>::OCC * 256 / TW < 1 ? 1 : RingCfg<T, R, TW, NP>::OCC * 256 / TW) : RingCfg<T, R, TW, NP>::OCC)))
+__global__ __launch_bounds__(TW, (RingCfg<T, R, TW, NP>::OCC))
 void ring_kernel(const DiskArgs<T> a) {
   using C = RingCfg<T, R, TW, NP>;
   using T2 = typename Vec2<T>::type;
@@ -1282,40 +1209,8 @@ void ring_kernel(const DiskArgs<T> a) {
   T2* const L = reinterpret_cast<T2*>(smrf_lds);         // [NP][NLEV][WP] of {row A, row B}
 
   const int tid = threadIdx.x;
-  // Workgroups are dealt round-robin over the 8 XCDs in dispatch order (x fastest), each XCD with
-  // its own L2.  Remap the tile so that an XCD owns a contiguous range of strips (all their
-  // segments): neighbouring strips share 2R halo columns, which then hit the same L2.  Placement
-  // only, any mapping is correct (MI355X_MICROARCH: workgroup dispatch, XCD placement).
-  int bx = blockIdx.x, by = blockIdx.y;
-#if SMRF_RING_XCD_REMAP == 2
-  {   // tuning build: an XCD owns a contiguous range of tiles in segment-major order (all strips of the same rows together)
-    const int total = gridDim.x * gridDim.y;
-    if ((total & 7) == 0) {
-      const int id = blockIdx.y * gridDim.x + blockIdx.x;
-      const int t = (id & 7) * (total >> 3) + (id >> 3);
-      bx = t % gridDim.x;
-      by = t / gridDim.x;
-    }
-  }
-#elif SMRF_RING_XCD_REMAP
-  if (a.plain_tiles) {
-  } else if ((gridDim.x & 7) == 0) {
-    const int id = blockIdx.y * gridDim.x + blockIdx.x, per = gridDim.x >> 3;
-    const int xcd = id & 7, slot = id >> 3;
-    bx = xcd * per + slot % per;
-    by = slot / per;
-  } else if (gridDim.x > 8 && a.seg_cls == 0) {
-    // any other strip count (round 5): an XCD owns a contiguous range of the tiles taken strip by strip (a strip's segments
-    // together), i.e. strips / 8 neighbouring strips and parts of the two at its ends.  Without it the halo columns of a
-    // raster of arbitrary width came from HBM again: 8193 columns fetched 5.6-7.3 B per cell and erosion pass against
-    // 4.7-5.3 at 8192 (profiles/r05_segment_balance.md section 5).  XCD x gets ceil((total - x) / 8) of the workgroups.
-    const int total = gridDim.x * gridDim.y, id = blockIdx.y * gridDim.x + blockIdx.x;
-    const int xcd = id & 7, slot = id >> 3, q = total >> 3, rem = total & 7;
-    const int t = xcd * q + (xcd < rem ? xcd : rem) + slot;
-    bx = t / (int)gridDim.y;
-    by = t % (int)gridDim.y;
-  }
-#endif
+  int bx, by;   // the general branch: equal segments only (ring_launch_np's residency classes count on `by` growing with the dispatch id)
+  smrf_xcd_tile(!SMRF_RING_XCD_REMAP || a.plain_tiles, [&] { return a.seg_cls == 0; }, bx, by);
 #ifdef SMRF_RING_DBG_CLOCK   // timing experiment only: the shader clock this workgroup ran at, left in the output's first two cells
   const unsigned long long dbg_t0 = __builtin_amdgcn_s_memtime(), dbg_q0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -1353,15 +1248,8 @@ void ring_kernel(const DiskArgs<T> a) {
     hl.pos = hl.act ? TW + h : TW;
   }
   const int hcol = smrf_fold(x0 - R + hl.pos, a.cols);
-  // workgroup-wide when the table is shared by several waves; a single-wave workgroup owns its
-  // table and only has to keep the compiler from moving LDS accesses across the phase boundary
-  auto phase_sync = [&]() {
-#ifdef SMRF_RING_DBG_NOSYNC   // timing experiment only (wrong results): what the workgroup barriers cost
-    asm volatile("" ::: "memory"); __builtin_amdgcn_wave_barrier(); return;
-#endif
-    if constexpr (TW > 64) __syncthreads();
-    else { asm volatile("" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
-  };
+  static_assert(TW == kRingTW, "the table is shared by the workgroup's four waves: workgroup barriers between the phases");
+  auto phase_sync = [&]() { __syncthreads(); };
   const bool flag = a.mask != nullptr;
   const int xc = x < a.cols ? x : a.cols - 1;
 
@@ -1404,15 +1292,6 @@ void ring_kernel(const DiskArgs<T> a) {
     xcb = (unsigned)xc * (unsigned)sizeof(T);
   }
   auto prefetch = [&]() {
-#ifdef SMRF_RING_DBG_NOLOAD   // timing experiment only (wrong results): the kernel without its loads from HBM
-    {
-      for (int p = 0; p < NP; ++p)
-        for (int i = 0; i < NPOS; ++i) { pf[p][i].x = (T)(tid + p); pf[p][i].y = (T)(tid - i); }
-      for (int j = 0; j < H::NJ; ++j) { pfh[j].x = (T)tid; pfh[j].y = (T)j; }
-      rf.advance(ROWS);
-      return;
-    }
-#endif
     const int l0 = rf.p - a.in_row0;
     if (rf.p + ROWS <= rf.n && l0 >= 0 && l0 + ROWS - 1 <= last_in) {
       // common case: ROWS consecutive rows inside the band, no reflection: one address, row strides
@@ -1532,13 +1411,6 @@ void ring_kernel(const DiskArgs<T> a) {
   auto epilogue = [&](int yyb) {
     const int yob = yyb - R;                               // first output row of the batch
     if (yob < ys || x >= a.cols) return;                   // (aligned: yob < ys means all rows are)
-#ifdef SMRF_RING_DBG_NOSTORE   // timing experiment only (wrong results): the kernel without its stores (kept alive by a test no value passes)
-    {
-      bool any = false;
-      for (int i = 0; i < ROWS; ++i) any |= (outv[i] == (T)-12345.678f) | (lastv[i] == (T)-12345.678f);
-      if (!any) return;
-    }
-#endif
     const long long off0 = (long long)(yob - a.out_row0) * a.ld + x;
     if (yob + ROWS <= ye && !a.nan_aware && !a.dense) {
       const int ro0 = yob - a.out_row0;
@@ -1561,21 +1433,17 @@ void ring_kernel(const DiskArgs<T> a) {
   };
   auto load_last = [&](int yyb) {
     if (!flag) return;
-#ifdef SMRF_RING_DBG_NOLOAD
-    { for (int i = 0; i < ROWS; ++i) lastv[i] = (T)-1e30f; return; }   // (no cell is flagged)
-#endif
     const int y0 = yyb - R - a.out_row0;
     if (y0 >= 0 && y0 + ROWS <= a.out_rows) {
       SMRF_MARK("last");
       if constexpr (BUF) {
         const unsigned s0 = (unsigned)(y0 - bl) * rowb;
 #pragma unroll
-        for (int i = 0; i < ROWS; ++i) lastv[i] = smrf_buf_load<SMRF_NT_LAST != 0>(rs_last, xcb, s0 + (unsigned)i * rowb, T());
+        for (int i = 0; i < ROWS; ++i) lastv[i] = smrf_buf_load(rs_last, xcb, s0 + (unsigned)i * rowb, T());
       } else {
       const T* l0 = a.last + (long long)y0 * a.ld + xc;
 #pragma unroll
-      for (int i = 0; i < ROWS; ++i)
-        lastv[i] = SMRF_NT_LAST ? __builtin_nontemporal_load(&l0[(long long)i * a.ld]) : l0[(long long)i * a.ld];
+      for (int i = 0; i < ROWS; ++i) lastv[i] = l0[(long long)i * a.ld];
       }
     } else {
       SMRF_MARK("rare");
@@ -1629,8 +1497,7 @@ void ring_kernel(const DiskArgs<T> a) {
     if constexpr (BAL) {
       // ring_build_consume with the halo cells as wave-jobs: every wave builds its own 256 cells' worth of each row
       // pair plus its share of the halo, so the waves reach the phase barriers together
-      __builtin_amdgcn_s_setprio(SMRF_RING_BUILD_PRIO);
-#ifndef SMRF_RING_DBG_NOBUILD
+      __builtin_amdgcn_s_setprio(kRingBuildPrio);
       ring_base<T, R, DIL, TW, NP, 1, 0>(L, par, tid, true, v);
       SMRF_MARK("build:halo");
       ring_base_halo<T, R, DIL, TW, NP>(L, par, hl, vh);
@@ -1641,7 +1508,6 @@ void ring_kernel(const DiskArgs<T> a) {
         ring_upper_halo<T, R, DIL, TW, NP>(L, hl, vh);
         phase_sync();
       }
-#endif
       __builtin_amdgcn_s_setprio(0);
       ring_consume<T, R, DIL, TW, NP>(L, par, tid, acc, outv);
     } else {
@@ -1679,7 +1545,7 @@ void ring_kernel(const DiskArgs<T> a) {
 
 template <typename T, int R, bool DIL, int NP>
 int ring_launch_np(const DiskArgs<T>& a_in, hipStream_t stream, bool probe_only, int* seg_if_launched) {
-  constexpr int TW = SMRF_RING_TW_OF(T, R);
+  constexpr int TW = kRingTW;
   using C = RingCfg<T, R, TW, NP>;
   auto kern = ring_kernel<T, R, DIL, TW, NP>;
   // workgroups one CU really holds (registers + LDS), per device: the attribute below is per device too
@@ -1791,7 +1657,7 @@ int ring_launch_np(const DiskArgs<T>& a_in, hipStream_t stream, bool probe_only,
 
 template <typename T, int R, bool DIL>
 int ring_launch(const DiskArgs<T>& a_in, hipStream_t stream) {
-  constexpr int TW = SMRF_RING_TW_OF(T, R);
+  constexpr int TW = kRingTW;
   constexpr int NP = SMRF_RING_NP(T, R);                 // the shifting ring's row pairs per batch where a radius is dual
   if constexpr (ring_tuned_inplace_dual<T>(R) && SMRF_RING_INPLACE(T, R)) {
     // Both forms exist (ring_inpl.inc): the in-place instance runs one more workgroup per CU (3 or 4 waves per SIMD), worth

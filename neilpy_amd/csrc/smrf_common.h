@@ -30,6 +30,35 @@ __host__ __device__ inline int smrf_fold(int i, int n) {
   return p < n ? p : p2 - 1 - p;
 }
 
+// XCD-aware tile placement of the strip kernels (ring, fused opening, incremental erosion): which tile (bx, by) = (strip,
+// row segment) this workgroup takes.  Workgroups are dealt round-robin over the 8 XCDs in dispatch order (x fastest), each
+// XCD with its own L2.  The tile is remapped so that an XCD owns a contiguous range of strips (all their segments):
+// neighbouring strips share their halo columns, which then hit the same L2.  Placement only, any mapping is correct
+// (MI355X_MICROARCH: workgroup dispatch, XCD placement).  plain: workgroup (x, y) takes tile (x, y).  general_allowed: a
+// callable, asked only where the second branch is reached (a kernel argument it reads is loaded there and nowhere else).
+template <typename F>
+__device__ __forceinline__ void smrf_xcd_tile(const bool plain, F&& general_allowed, int& bx, int& by) {
+  bx = blockIdx.x;
+  by = blockIdx.y;
+  if (plain) {
+  } else if ((gridDim.x & 7) == 0) {
+    const int id = blockIdx.y * gridDim.x + blockIdx.x, per = gridDim.x >> 3;
+    const int xcd = id & 7, slot = id >> 3;
+    bx = xcd * per + slot % per;
+    by = slot / per;
+  } else if (gridDim.x > 8 && general_allowed()) {
+    // any other strip count (round 5): an XCD owns a contiguous range of the tiles taken strip by strip (a strip's segments
+    // together), i.e. strips / 8 neighbouring strips and parts of the two at its ends.  Without it the halo columns of a
+    // raster of arbitrary width came from HBM again: 8193 columns fetched 5.6-7.3 B per cell and erosion pass against
+    // 4.7-5.3 at 8192 (profiles/r05_segment_balance.md section 5).  XCD x gets ceil((total - x) / 8) of the workgroups.
+    const int total = gridDim.x * gridDim.y, id = blockIdx.y * gridDim.x + blockIdx.x;
+    const int xcd = id & 7, slot = id >> 3, q = total >> 3, rem = total & 7;
+    const int t = xcd * q + (xcd < rem ? xcd : rem) + slot;
+    bx = t / (int)gridDim.y;
+    by = t % (int)gridDim.y;
+  }
+}
+
 // The SMRF_* environment switches (developer A/B runs; the parity tests force every launch variant through them), read
 // once by core.hip - smrf_switches_reload() of the C ABI reads them again.  -1 / 0 = "by the library's own rule".
 struct SmrfSwitches {

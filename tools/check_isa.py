@@ -5,8 +5,12 @@ the LDS rate of the single forms on gfx950, MI355X_MICROARCH LDS table; the kern
 inline-asm reads and staging stores).  Exit code 1 if either is found.
 
     python tools/check_isa.py [-j 8]
+
+--dump DIR also compiles incero.hip and writes DIR/manifest.txt, one line per kernel: symbol, VGPRs, SGPRs, scratch and LDS
+bytes, sha256 of its instructions.  `diff` of two trees' manifests shows whether a change reached the generated code.
 """
 import argparse
+import hashlib
 import os
 import re
 import subprocess
@@ -82,14 +86,30 @@ def lds_hazards(text):
     return bad
 
 
+def manifest(text):
+    """One line per kernel of an assembly file.  The instruction text is hashed without comments and directives and with
+    the function's number taken out of its local labels, so that the order of the functions in the unit does not show."""
+    out = []
+    for m in re.finditer(r"^\s*\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel", text, re.S | re.M):
+        sym, desc = m.groups()
+        body = text[text.index("\n%s:" % sym):m.start()].split("\n", 2)[2]
+        nums = [re.search(r"\.amdhsa_%s (\d+)" % k, desc).group(1)
+                for k in ("next_free_vgpr", "next_free_sgpr", "private_segment_fixed_size", "group_segment_fixed_size")]
+        ins = [re.sub(r"\.LBB\d+_", ".LBB_", l.split(";")[0].strip()) for l in body.splitlines()]
+        ins = [l for l in ins if l and (l[0] != "." or l.endswith(":"))]
+        out.append(" ".join([sym] + nums + [hashlib.sha256("\n".join(ins).encode()).hexdigest()]))
+    return out
+
+
 DEFS = []
 
 
 def one(job):
     part, f64, tmp = job
-    if part < 0:                                           # the chained / table-free launches (both dtypes in one unit)
-        out = os.path.join(tmp, "chain.s")
-        cmd = [hipcc()] + [f for f in FLAGS if f != "-fPIC"] + DEFS + ["--offload-device-only", "-S", os.path.join(CSRC, "chain.hip"),
+    if part < 0:                                           # chain.hip: the chained / table-free launches (both dtypes in one
+        name = "chain" if part == -1 else "incero"         # unit); incero.hip (--dump only): the incremental erosion
+        out = os.path.join(tmp, name + ".s")
+        cmd = [hipcc()] + [f for f in FLAGS if f != "-fPIC"] + DEFS + ["--offload-device-only", "-S", os.path.join(CSRC, name + ".hip"),
                                                                "-o", out]
     else:
         out = os.path.join(tmp, "ring_%d_%d.s" % (f64, part))
@@ -114,7 +134,7 @@ def one(job):
     bad += ["%d x %s in %s" % (n, op, k) for (k, op), n in fused.items()]
     hz = lds_hazards(text)
     bad += hz[:5] + (["... and %d more in-flight uses" % (len(hz) - 5)] if len(hz) > 5 else [])
-    return part, f64, bad
+    return part, f64, bad, manifest(text)
 
 
 def main():
@@ -122,17 +142,22 @@ def main():
     ap.add_argument("-j", type=int, default=min(8, os.cpu_count() or 1))
     ap.add_argument("--defs", default="", help="extra compiler flags (variant builds), space separated")
     ap.add_argument("--f32-only", action="store_true")
+    ap.add_argument("--dump", metavar="DIR", help="write DIR/manifest.txt (see above)")
     a = ap.parse_args()
     DEFS[:] = [d for d in a.defs.split() if d]
     with tempfile.TemporaryDirectory() as tmp:
-        jobs = [(p, f, tmp) for f in ((0,) if a.f32_only else (0, 1)) for p in range(RING_PARTS)] + [(-1, 0, tmp)]
+        jobs = [(p, f, tmp) for f in ((0,) if a.f32_only else (0, 1)) for p in range(RING_PARTS)] + [(-1, 0, tmp)] + ([(-2, 0, tmp)] if a.dump else [])
         with ThreadPoolExecutor(max_workers=a.j) as ex:
             res = list(ex.map(one, jobs))
+    if a.dump:
+        os.makedirs(a.dump, exist_ok=True)
+        with open(os.path.join(a.dump, "manifest.txt"), "w") as f:
+            f.write("".join(l + "\n" for l in sorted(l for r in res for l in r[3])))
     n = 0
-    for part, f64, bad in res:
+    for part, f64, bad, _ in res:
         for b in bad:
             n += 1
-            print("%s: %s" % ("chain" if part < 0 else "ring_%s_p%d" % ("f64" if f64 else "f32", part), b))
+            print("%s: %s" % ("incero" if part == -2 else "chain" if part < 0 else "ring_%s_p%d" % ("f64" if f64 else "f32", part), b))
     print("%d finding(s) in %d translation units" % (n, len(res)))
     return 1 if n else 0
 
