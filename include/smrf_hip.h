@@ -424,6 +424,28 @@ SMRF_API int smrf_surface_f64(const double* d_Z, int rows, int cols, int mode, i
                      double p2, double p3, const double* d_angles, int n_angles, void* d_out0, void* d_out1,
                      void* d_out2, void* d_out3, void* d_out4, void* d_out5, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * nearest-source infill: exact Euclidean feature transform (neilpy_amd/nearest.py)
+ * ------------------------------------------------------------------------------------------ */
+/* inpaint_nearest(), neilpy.py:1277.  A hole is a cell that is not finite (NaN, +-inf), a source any other cell.  Every
+ * hole of the contiguous rows x cols raster d_in takes the bits of its nearest source in squared Euclidean index
+ * distance; among sources at the minimal distance the lowest row, then the lowest column wins.  Sources are copied.
+ * d_out (may equal d_in, may be NULL), d_src_index (flat index rows * cols of the chosen source, the cell's own for a
+ * source; may be NULL) and d_dist2 (the exact squared distance, unsigned 32-bit; may be NULL) are written for every
+ * cell.  A raster without a source comes back unchanged with index -1 and distance 0xFFFFFFFF.  rows, cols <= 46341
+ * (the largest squared distance fits 32 bits).  Workspace: smrf_nearest_workspace_bytes() (integer planes only,
+ * elem_size is 4 or 8 and does not change it). */
+SMRF_API size_t smrf_nearest_workspace_bytes(int rows, int cols, int elem_size);
+SMRF_API int smrf_nearest_f32(const float* d_in, float* d_out, int64_t* d_src_index, uint32_t* d_dist2, int rows,
+                     int cols, void* d_workspace, size_t workspace_bytes, void* stream);
+SMRF_API int smrf_nearest_f64(const double* d_in, double* d_out, int64_t* d_src_index, uint32_t* d_dist2, int rows,
+                     int cols, void* d_workspace, size_t workspace_bytes, void* stream);
+/* The planes nearest_source() returns, from the two above over n cells: d_dist = sqrt(d_dist2) in float64 (inf where
+ * there is no source), d_row / d_col = the source's row and column (-1 where there is none).  d_dist alone, or d_row
+ * and d_col together, may be NULL. */
+SMRF_API int smrf_nearest_planes(const int64_t* d_src_index, const uint32_t* d_dist2, int64_t n, int cols,
+                     double* d_dist, int64_t* d_row, int64_t* d_col, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,8 @@ Drop-in for ``neilpy.smrf`` / ``progressive_filter`` / ``create_dem`` /
 in hand-written gfx950 HIP kernels in ``libsmrf_hip.so`` (C ABI: ``include/smrf_hip.h``);
 there is no CPU fallback.  ``openness`` / ``skyview_factor`` / ``geomorphons`` and their kin (neilpy_amd/terrain.py)
 analyse the resulting DTM with the same kernels-only rule, and so do its local surface derivatives ``slope`` / ``aspect``
-/ ``hillshade`` / the curvatures (neilpy_amd/surface.py).
+/ ``hillshade`` / the curvatures (neilpy_amd/surface.py).  ``inpaint_nearest`` is the third hole filler, an exact nearest-cell
+infill, and ``nearest_source`` the distance / index planes behind it (neilpy_amd/nearest.py).
 """
 from ._lib import SmrfHipError, load as load_library, LIB_PATH          # noqa: F401
 from .affine import Affine, edges_from_IT, from_origin, write_worldfile                 # noqa: F401
@@ -13,6 +14,7 @@ from .api import (create_dem, dilation, disk, erosion, inpaint_nans_by_fda, inpa
                   last_stats,
                   opening, progressive_filter, pssm, smrf)
 from .las import read_las, read_las_xyz, write_las                         # noqa: F401
+from .nearest import inpaint_nearest, nearest_source                      # noqa: F401
 from .surface import (aspect, curvature, esri_curvature, esri_slope, evans_curvature, hillshade,   # noqa: F401
                       multiple_illumination, slope, wilson_gallant_curvature, z_factor,
                       zevenbergen_and_thorne_curvature)

@@ -89,6 +89,10 @@ SIGNATURES = {
     "smrf_terrain_rays_f64": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _i, _p, _i, _i, _d, _i, _p, _p, _p, _p, _i, _p]),
     "smrf_surface_f32": (_i, [_p, _i, _i, _i, _i, _d, _d, _d, _d, _p, _i, _p, _p, _p, _p, _p, _p, _p]),
     "smrf_surface_f64": (_i, [_p, _i, _i, _i, _i, _d, _d, _d, _d, _p, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "smrf_nearest_workspace_bytes": (_sz, [_i, _i, _i]),
+    "smrf_nearest_f32": (_i, [_p, _p, _p, _p, _i, _i, _p, _sz, _p]),
+    "smrf_nearest_f64": (_i, [_p, _p, _p, _p, _i, _i, _p, _sz, _p]),
+    "smrf_nearest_planes": (_i, [_p, _p, _i64, _i, _p, _p, _p, _p]),
 }
 
 _lib = None
