@@ -280,27 +280,56 @@ def create_dem(x, y, z, cellsize=1, bin_type='max', inpaint=False, edges=None, u
     xd, yd, zd = _points_to_device(x, y, z)
     grid, _, t = _create_dem_device(xd, yd, zd, cellsize, bin_type, edges)
     if inpaint == True:  # noqa: E712  (the reference's own test, :1163)
-        _springs_device(grid)
+        _lsqr_device(grid, "springs", "inpaint")
     return (grid if was_tensor else _d2h(grid)), t
 
 
 # ------------------------------------------------------------------------------------------
-# inpaint_nans_by_springs  (neilpy.py:1227-1271)
+# inpaint_nans_by_springs  (neilpy.py:1227-1271), inpaint_nans_by_fda  (neilpy.py:1170-1216)
 # ------------------------------------------------------------------------------------------
-def _springs_device(Ad, key="inpaint"):
-    """In-place LSQR spring fill of a contiguous float64 CUDA raster; returns (istop, itn)."""
+def _lsqr_device(Ad, export, key):
+    """In-place LSQR fill of a contiguous float64 CUDA raster by ``smrf_<export>_lsqr_f64``; returns (istop, itn)."""
     torch = _torch()
     lib = _lib.load()
     rows, cols = Ad.shape
     if rows == 0 or cols == 0:
         return 0, 0
-    nbytes = lib.smrf_springs_workspace_bytes(rows, cols)
+    nbytes = getattr(lib, "smrf_%s_workspace_bytes" % export)(rows, cols)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=Ad.device)
     istop, itn, nunk = C.c_int(0), C.c_int64(0), C.c_int64(0)
-    _lib.check(lib.smrf_springs_lsqr_f64(_ptr(Ad), rows, cols, 1e-6, 1e-6, 1e8, -1, C.byref(istop), C.byref(itn),
-                                         C.byref(nunk), _ptr(ws), nbytes, _stream()))
+    _lib.check(getattr(lib, "smrf_%s_lsqr_f64" % export)(_ptr(Ad), rows, cols, 1e-6, 1e-6, 1e8, -1, C.byref(istop),
+                                                         C.byref(itn), C.byref(nunk), _ptr(ws), nbytes, _stream()))
     last_stats[key] = dict(istop=istop.value, itn=itn.value, n_unknown=nunk.value)
     return istop.value, itn.value
+
+
+def _inpaint(A, inplace, export, key, dtype_error, check_shape=None):
+    """Tensor / NumPy / ``inplace`` skeleton of the two LSQR inpaints; ``check_shape(shape)`` holds a function's own test."""
+    torch = _torch()
+    if _is_tensor(A):
+        if A.dtype != torch.float64:
+            raise TypeError(dtype_error)
+        if check_shape:
+            check_shape(tuple(A.shape))
+        work = A if (inplace and A.is_cuda and A.is_contiguous()) else _to_device(A).clone()
+        _lsqr_device(work, export, key)
+        if inplace:
+            if work is not A:
+                A.copy_(work)
+            return None
+        return work
+    arr = np.asarray(A)
+    if arr.ndim != 2:
+        raise ValueError("expected a 2-D raster")
+    if check_shape:
+        check_shape(arr.shape)
+    work = _to_device(arr.astype(np.float64, copy=False), torch.float64).clone()
+    _lsqr_device(work, export, key)
+    out = _d2h(work)
+    if inplace:
+        A[...] = out
+        return None
+    return out
 
 
 @_device_scoped
@@ -310,46 +339,12 @@ def inpaint_nans_by_springs(A, inplace=False, neighbors=4):
     Same arguments and results as neilpy.inpaint_nans_by_springs (``neighbors`` is accepted and
     ignored there too); ``inplace=True`` writes into ``A`` and returns ``None``.
     """
-    torch = _torch()
-    if _is_tensor(A):
-        if A.dtype != torch.float64:
-            raise TypeError("inpaint_nans_by_springs works in float64, as the reference does")
-        work = A if (inplace and A.is_cuda and A.is_contiguous()) else _to_device(A).clone()
-        _springs_device(work)
-        if inplace:
-            if work is not A:
-                A.copy_(work)
-            return None
-        return work
-    arr = np.asarray(A)
-    if arr.ndim != 2:
-        raise ValueError("expected a 2-D raster")
-    work = _to_device(arr.astype(np.float64, copy=False), torch.float64).clone()
-    _springs_device(work)
-    out = _d2h(work)
-    if inplace:
-        A[...] = out
-        return None
-    return out.astype(arr.dtype, copy=False) if arr.dtype == np.float64 else out
+    return _inpaint(A, inplace, "springs", "inpaint", "inpaint_nans_by_springs works in float64, as the reference does")
 
 
-# ------------------------------------------------------------------------------------------
-# inpaint_nans_by_fda  (neilpy.py:1170-1216)
-# ------------------------------------------------------------------------------------------
-def _fda_device(Ad, key="inpaint_fda"):
-    """In-place LSQR finite-difference fill of a contiguous float64 CUDA raster; returns (istop, itn)."""
-    torch = _torch()
-    lib = _lib.load()
-    rows, cols = Ad.shape
-    if rows == 0 or cols == 0:
-        return 0, 0
-    nbytes = lib.smrf_fda_workspace_bytes(rows, cols)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=Ad.device)
-    istop, itn, nunk = C.c_int(0), C.c_int64(0), C.c_int64(0)
-    _lib.check(lib.smrf_fda_lsqr_f64(_ptr(Ad), rows, cols, 1e-6, 1e-6, 1e8, -1, C.byref(istop), C.byref(itn),
-                                     C.byref(nunk), _ptr(ws), nbytes, _stream()))
-    last_stats[key] = dict(istop=istop.value, itn=itn.value, n_unknown=nunk.value)
-    return istop.value, itn.value
+def _fda_shape(shape):
+    if len(shape) != 2 or shape[0] < 2 or shape[1] < 2:
+        raise ValueError("negative dimensions are not allowed")      # the reference's np.ones(2*n*(m-2)) at :1190
 
 
 @_device_scoped
@@ -360,31 +355,7 @@ def inpaint_nans_by_fda(A, fast=True, inplace=False):
     that cannot touch a NaN in the reference, so both settings give the same raster (and run the
     same kernels here).  ``inplace=True`` writes into ``A`` and returns ``None``.
     """
-    torch = _torch()
-    if _is_tensor(A):
-        if A.dtype != torch.float64:
-            raise TypeError("inpaint_nans_by_fda works in float64")
-        if A.dim() != 2 or A.shape[0] < 2 or A.shape[1] < 2:
-            raise ValueError("negative dimensions are not allowed")
-        work = A if (inplace and A.is_cuda and A.is_contiguous()) else _to_device(A).clone()
-        _fda_device(work)
-        if inplace:
-            if work is not A:
-                A.copy_(work)
-            return None
-        return work
-    arr = np.asarray(A)
-    if arr.ndim != 2:
-        raise ValueError("expected a 2-D raster")
-    if arr.shape[0] < 2 or arr.shape[1] < 2:
-        raise ValueError("negative dimensions are not allowed")      # the reference's np.ones(2*n*(m-2)) at :1190
-    work = _to_device(arr.astype(np.float64, copy=False), torch.float64).clone()
-    _fda_device(work)
-    out = _d2h(work)
-    if inplace:
-        A[...] = out
-        return None
-    return out
+    return _inpaint(A, inplace, "fda", "inpaint_fda", "inpaint_nans_by_fda works in float64", _fda_shape)
 
 
 # ------------------------------------------------------------------------------------------
@@ -446,7 +417,7 @@ def smrf(x, y, z, cellsize=1, windows=5, slope_threshold=.15, elevation_threshol
         windows = np.arange(windows) + 1
     xd, yd, zd = _points_to_device(x, y, z)
     Zmin, empty, t = _create_dem_device(xd, yd, zd, cellsize, 'min', None)          # :1741-1742
-    _springs_device(Zmin, "inpaint1")                                               # :1743
+    _lsqr_device(Zmin, "springs", "inpaint1")                                    # :1743
     low_thr = low_filter_slope * (np.array([1]) * cellsize)
     lib = _lib.load()
     neg = torch.empty_like(Zmin)
@@ -455,13 +426,13 @@ def smrf(x, y, z, cellsize=1, windows=5, slope_threshold=.15, elevation_threshol
     del neg
     if low_outlier_fill:                                                            # :1747-1749
         _lib.check(lib.smrf_mask_apply_f64(_ptr(Zmin), _ptr(low), None, None, None, Zmin.numel(), _stream()))
-        _springs_device(Zmin, "inpaint1b")
+        _lsqr_device(Zmin, "springs", "inpaint1b")
     thr = slope_threshold * (windows * cellsize)
     obj, drop = _progressive_filter_device(Zmin, windows, thr, bool(return_extras), nan_aware=0)       # :1752-1755
     object_cells = torch.empty_like(obj)
     _lib.check(lib.smrf_mask_apply_f64(_ptr(Zmin), _ptr(empty), _ptr(low), _ptr(obj), _ptr(object_cells),
                                        Zmin.numel(), _stream()))                    # :1762-1763
-    _springs_device(Zmin, "inpaint2")                                               # :1764
+    _lsqr_device(Zmin, "springs", "inpaint2")                                    # :1764
     Zpro_d = Zmin
     elev_d, slope_d, isobj_d, r_d, c_d = _classify_points_device(Zpro_d, t, cellsize, xd, yd, zd, elevation_threshold,
                                                                  elevation_scaler)

@@ -10,7 +10,8 @@
 // scipy.sparse.linalg.lsqr(fda[k][:, nan], (-fda[:, known] @ A[known])[k]) with default
 // tolerances (:1210).  `fast=True` only pre-filters rows that could not touch a NaN anyway, so it
 // does not change the result.  As with the springs, the answer is LSQR's iterate at its stop, so
-// this file follows scipy's recurrence (lsqr_core.h) and its products' accumulation order:
+// this file follows scipy's recurrence (lsqr_core.h: scalar steps, x / w / dk step and driver, shared
+// with springs.hip) and its products' accumulation order:
 //   - x, v, w are rasters that stay 0 on known cells; u is one raster over equation cells with the
 //     multiplicity cnt[i] (0..5 = NaN cells among centre/up/down/left/right of the stencil) beside it;
 //   - A v on an equation cell: sum over its NaN stencil cells in ascending flat index (up, left,
@@ -50,13 +51,6 @@ __global__ __launch_bounds__(256) void fda_mask_kernel(const double* __restrict_
   if (threadIdx.x == 0) b.part[blockIdx.x] = t;
 }
 
-__global__ void fda_count(const Fda b) {
-  Sc* sc = b.sc;
-  sc->nunk = (long long)b.red[0];
-  if (sc->iter_lim < 0) sc->iter_lim = 2 * sc->nunk;
-  if (sc->nunk == 0) sc->done = 1;
-}
-
 // multiplicity and right-hand side of every equation cell: rhs = (-fda[:, known]) @ A[known]
 __global__ __launch_bounds__(256) void fda_rhs_kernel(const double* __restrict__ A, const Fda b) {
   __shared__ double red[4];
@@ -84,17 +78,6 @@ __global__ __launch_bounds__(256) void fda_rhs_kernel(const double* __restrict__
   }
   const double t = block_sum(s, red);
   if (threadIdx.x == 0) b.part[blockIdx.y * gridDim.x + blockIdx.x] = t;
-}
-
-__global__ void fda_bnorm(const Fda b) {
-  Sc* sc = b.sc;
-  const double bn = sqrt(b.red[0]);
-  sc->bnorm = bn;
-  sc->beta = bn;
-  sc->beta_pos = bn > 0;
-  sc->inv_beta = bn > 0 ? 1 / bn : 1.0;
-  sc->alfa = 0.0;
-  sc->inv_alfa = 1.0;
 }
 
 // A^T u_s on one NaN cell: the equations whose stencil holds it, each cnt times, in SciPy's CSC order
@@ -147,38 +130,22 @@ __global__ __launch_bounds__(256) void fda_atu_kernel(const Fda b) {
   if (threadIdx.x == 0) b.part[SMRF_TILE_SLOT(tl)] = t;
 }
 
-// The iteration's v pass with the x / w / dk steps riding in it (round 5; springs.hip: atuxw_kernel has the derivation):
-//   w_{k-1} = v_{k-1} / alfa_{k-1} + t2_{k-1} w_{k-2} (k = 1: w_0 = v_0 / alfa_0), dk_k = w_{k-1} / rho_k, |dk|^2,
-//   k even: x_k = (x_{k-2} + t1_{k-1} w_{k-2}) + t1_k w_{k-1};  v_k = A^T u_k - beta_k v_{k-1}, |v|^2.
-// part[0..] <- |v|^2, part[MAXB..] <- |dk|^2.  Same operations per entry and the same cells per partial sum as the
-// xw + atu passes it replaces: x, istop, itn are bit-identical.
+// The iteration's v pass with the x / w / dk steps riding in it (lsqr_core.h: lsqr_xw_step has the derivation).
+// part[0..] <- |v|^2, part[MAXB..] <- |dk|^2.
 __global__ __launch_bounds__(256) void fda_atuxw_kernel(const Fda b) {
   __shared__ double red[4];
   __shared__ double red2[4];
   const Sc* sc = b.sc;
   if (stopped(sc)) return;
-  const long long itn = sc->itn;
-  const bool first = itn == 0, xupd = (itn & 1) != 0, bpos = sc->beta_pos != 0;
-  const double ib = sc->inv_beta, ia = sc->inv_alfa, beta = sc->beta;
-  const double t1 = sc->t1, t1p = sc->t1_prev, t2 = sc->t2, ir = sc->inv_rho;
+  const AtuxwSc q = atuxw_scalars(sc);
   double s = 0.0, sd = 0.0;
   const LsqrTile tl = lsqr_tile(b.nxcd);
   SMRF_FOR_CELLS_T(tl, b.rows, b.cols, b.cols) {
     if (!b.hole[i]) continue;
-    const double vs = ia * b.v[i];
-    double wn;
-    if (first) {
-      wn = vs;
-    } else {
-      const double wo = b.w[i];
-      wn = vs + t2 * wo;
-      if (xupd) b.x[i] = (b.x[i] + t1p * wo) + t1 * wn;
-    }
-    b.w[i] = wn;
-    const double dk = ir * wn;
-    sd += dk * dk;
-    if (bpos) {
-      const double nv = fda_col_dot(b, i, r, c, ib) - beta * vs;
+    const LsqrXw o = lsqr_xw_step(q, b.x, b.v, b.w, i);
+    sd += o.dk * o.dk;
+    if (q.bpos) {
+      const double nv = fda_col_dot(b, i, r, c, q.ib) - q.beta * o.vs;
       b.v[i] = nv;
       s += nv * nv;
     }
@@ -186,17 +153,6 @@ __global__ __launch_bounds__(256) void fda_atuxw_kernel(const Fda b) {
   const double t = block_sum(s, red);
   const double td = block_sum(sd, red2);
   if (threadIdx.x == 0) { b.part[SMRF_TILE_SLOT(tl)] = t; b.part[MAXB + SMRF_TILE_SLOT(tl)] = td; }
-}
-
-__global__ void fda_init_alfa(const Fda b) {
-  Sc* sc = b.sc;
-  if (sc->done) return;
-  const double a = sc->beta_pos ? sqrt(b.red[0]) : 0.0;
-  sc->alfa = a;
-  sc->inv_alfa = a > 0 ? 1 / a : 1.0;
-  sc->rhobar = a;
-  sc->phibar = sc->beta;
-  if (a * sc->beta == 0) sc->done = 1;      // arnorm == 0: x = 0 is the answer (lsqr.py:386-390)
 }
 
 // A v_s on one equation cell (ascending flat index of the stencil's NaN cells)
@@ -233,13 +189,11 @@ __global__ __launch_bounds__(256) void fda_av_kernel(const Fda b) {
 
 __global__ __launch_bounds__(256) void fda_scatter_kernel(double* __restrict__ A, const Fda b) {
   const long long n = (long long)b.rows * b.cols;
-  const bool pend = (b.sc->itn & 1) != 0;                 // stopped at an odd iteration: x still lacks t1_k w_{k-1} (fda_atuxw_kernel)
+  const bool pend = lsqr_x_pending(b.sc);
   const double t1 = b.sc->t1;
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
     if (b.hole[i]) A[i] = pend ? b.x[i] + t1 * b.w[i] : b.x[i];
 }
-
-size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct FdaLayout { size_t plane, bytes, x, v, w, u, hole, cnt, part, red, sc, total; };
 FdaLayout fda_layout(int rows, int cols) {
@@ -260,6 +214,20 @@ FdaLayout fda_layout(int rows, int cols) {
   L.total = o;
   return L;
 }
+Fda fda_bind(void* ws, int rows, int cols) {
+  const FdaLayout L = fda_layout(rows, cols);
+  char* p = (char*)ws;
+  Fda b;
+  b.x = (double*)(p + L.x); b.v = (double*)(p + L.v); b.w = (double*)(p + L.w); b.u = (double*)(p + L.u);
+  b.hole = (uint8_t*)(p + L.hole); b.cnt = (uint8_t*)(p + L.cnt);
+  b.part = (double*)(p + L.part); b.red = (double*)(p + L.red); b.sc = (Sc*)(p + L.sc);
+  b.rows = rows; b.cols = cols; b.nxcd = lsqr_xcd_count();
+  return b;
+}
+// 1-D launch of the mask and scatter kernels
+int fda_grid1d(int rows, int cols) {
+  return (int)std::max<long long>(1, std::min<long long>(((long long)rows * cols + 255) / 256, MAXB));
+}
 
 }  // namespace
 
@@ -273,63 +241,27 @@ int smrf_fda_lsqr_f64(double* d_A, int rows, int cols, double atol, double btol,
   hipStream_t stream = (hipStream_t)stream_;
   if (!d_A || !h_istop || !h_itn) return smrf_fail(SMRF_E_ARG, "null pointer");
   if (rows < 1 || cols < 1) return smrf_fail(SMRF_E_ARG, "bad raster size %d x %d", rows, cols);
-  const FdaLayout L = fda_layout(rows, cols);
-  if (!d_workspace || workspace_bytes < L.total) return smrf_fail(SMRF_E_WORKSPACE, "fda workspace too small");
-  char* p = (char*)d_workspace;
-  Fda b;
-  b.x = (double*)(p + L.x); b.v = (double*)(p + L.v); b.w = (double*)(p + L.w); b.u = (double*)(p + L.u);
-  b.hole = (uint8_t*)(p + L.hole); b.cnt = (uint8_t*)(p + L.cnt);
-  b.part = (double*)(p + L.part); b.red = (double*)(p + L.red); b.sc = (Sc*)(p + L.sc);
-  b.rows = rows; b.cols = cols; b.nxcd = lsqr_xcd_count();
-
-  Sc h{};
-  h.atol = atol; h.btol = btol; h.ctol = conlim > 0 ? 1 / conlim : 0.0;
-  h.cs2 = -1.0; h.iter_lim = iter_lim;
-  SMRF_HIP_CHECK(hipMemcpyAsync(b.sc, &h, sizeof(h), hipMemcpyHostToDevice, stream));
-  SMRF_HIP_CHECK(hipStreamSynchronize(stream));   // h is a stack object
-
-  const long long n = (long long)rows * cols;
-  const int nb1 = (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, MAXB));
-  const int cb = (cols + 255) / 256;
-  const dim3 g2(cb, std::max(1, std::min(rows, MAXB / std::max(cb, 1))));
+  if (!d_workspace || workspace_bytes < fda_layout(rows, cols).total) return smrf_fail(SMRF_E_WORKSPACE, "fda workspace too small");
+  const Fda b = fda_bind(d_workspace, rows, cols);
+  if (int rc = lsqr_init_scalars(b.sc, atol, btol, conlim, iter_lim, stream)) return rc;
+  const int nb1 = fda_grid1d(rows, cols);
+  const dim3 g2 = lsqr_grid2d(rows, cols);
   const int nb = (int)(g2.x * g2.y);
   auto reduce = [&](int count) {
     hipLaunchKernelGGL(reduce_kernel, dim3(1), dim3(256), 0, stream, (const double*)b.part, count, b.red);
   };
   hipLaunchKernelGGL(fda_mask_kernel, dim3(nb1), dim3(256), 0, stream, (const double*)d_A, b);
   reduce(nb1);
-  hipLaunchKernelGGL(fda_count, dim3(1), dim3(1), 0, stream, b);
+  hipLaunchKernelGGL((setup_scalar_kernel<LSQR_COUNT, Fda>), dim3(1), dim3(1), 0, stream, b);
   hipLaunchKernelGGL(fda_rhs_kernel, g2, dim3(256), 0, stream, (const double*)d_A, b);
   reduce(nb);
-  hipLaunchKernelGGL(fda_bnorm, dim3(1), dim3(1), 0, stream, b);
+  hipLaunchKernelGGL((setup_scalar_kernel<LSQR_BNORM, Fda>), dim3(1), dim3(1), 0, stream, b);
   hipLaunchKernelGGL(fda_atu_kernel, g2, dim3(256), 0, stream, b);
   reduce(nb);
-  hipLaunchKernelGGL(fda_init_alfa, dim3(1), dim3(1), 0, stream, b);
+  hipLaunchKernelGGL((setup_scalar_kernel<LSQR_INIT_ALFA, Fda>), dim3(1), dim3(1), 0, stream, b);
   SMRF_LAUNCH_CHECK();
-
   Sc out{};
-  SMRF_HIP_CHECK(hipMemcpyAsync(&out, b.sc, sizeof(out), hipMemcpyDeviceToHost, stream));
-  SMRF_HIP_CHECK(hipStreamSynchronize(stream));
-  const long long lim = out.iter_lim;
-  // Iteration k = [w_{k-1}, dk_k, (x), v_k] [alfa_k, rotation, tests_k] [u_{k+1}] [beta_{k+1}, rho_{k+1}], as in springs.hip
-  if (!out.done && out.istop == 0 && out.itn < lim) {
-    hipLaunchKernelGGL(fda_av_kernel, g2, dim3(256), 0, stream, b);
-    hipLaunchKernelGGL((reduce_scalar_kernel<4, Fda>), dim3(1), dim3(256), 0, stream, b, nb);
-    SMRF_LAUNCH_CHECK();
-  }
-  int chunk = 4;
-  while (!out.done && out.istop == 0 && out.itn < lim) {
-    for (int k = 0; k < chunk; ++k) {
-      hipLaunchKernelGGL(fda_atuxw_kernel, g2, dim3(256), 0, stream, b);
-      hipLaunchKernelGGL((reduce_scalar_kernel<3, Fda>), dim3(1), dim3(256), 0, stream, b, nb);
-      hipLaunchKernelGGL(fda_av_kernel, g2, dim3(256), 0, stream, b);
-      hipLaunchKernelGGL((reduce_scalar_kernel<4, Fda>), dim3(1), dim3(256), 0, stream, b, nb);
-    }
-    SMRF_LAUNCH_CHECK();
-    SMRF_HIP_CHECK(hipMemcpyAsync(&out, b.sc, sizeof(out), hipMemcpyDeviceToHost, stream));
-    SMRF_HIP_CHECK(hipStreamSynchronize(stream));
-    chunk = std::min(64, chunk * 2);
-  }
+  if (int rc = lsqr_iterate(b, fda_atuxw_kernel, fda_av_kernel, g2, nb, 64, stream, out)) return rc;
   if (out.nunk > 0) {
     hipLaunchKernelGGL(fda_scatter_kernel, dim3(nb1), dim3(256), 0, stream, d_A, b);
     SMRF_LAUNCH_CHECK();
@@ -352,23 +284,12 @@ int smrf_fda_apply_f64(const double* d_A, int rows, int cols, const double* d_v,
   hipStream_t stream = (hipStream_t)stream_;
   if (!d_A || !d_v || !d_u || !d_rhs || !d_cnt || !d_Av || !d_Atu) return smrf_fail(SMRF_E_ARG, "null pointer");
   if (rows < 1 || cols < 1) return smrf_fail(SMRF_E_ARG, "bad raster size %d x %d", rows, cols);
-  const FdaLayout L = fda_layout(rows, cols);
-  if (!d_workspace || workspace_bytes < L.total) return smrf_fail(SMRF_E_WORKSPACE, "fda workspace too small");
-  char* p = (char*)d_workspace;
-  Fda b;
-  b.x = (double*)(p + L.x); b.v = (double*)(p + L.v); b.w = (double*)(p + L.w); b.u = (double*)(p + L.u);
-  b.hole = (uint8_t*)(p + L.hole); b.cnt = (uint8_t*)(p + L.cnt);
-  b.part = (double*)(p + L.part); b.red = (double*)(p + L.red); b.sc = (Sc*)(p + L.sc);
-  b.rows = rows; b.cols = cols; b.nxcd = lsqr_xcd_count();
-  Sc h{};
-  h.cs2 = -1.0; h.iter_lim = -1;
-  h.inv_alfa = 1.0; h.inv_beta = 1.0; h.beta_pos = 1;     // alfa = beta = 0: the kernels compute the bare products
-  SMRF_HIP_CHECK(hipMemcpyAsync(b.sc, &h, sizeof(h), hipMemcpyHostToDevice, stream));
-  SMRF_HIP_CHECK(hipStreamSynchronize(stream));
+  if (!d_workspace || workspace_bytes < fda_layout(rows, cols).total) return smrf_fail(SMRF_E_WORKSPACE, "fda workspace too small");
+  const Fda b = fda_bind(d_workspace, rows, cols);
+  if (int rc = lsqr_init_scalars(b.sc, 0.0, 0.0, 0.0, -1, stream, true)) return rc;   // alfa = beta = 0: the bare products
   const size_t n = (size_t)rows * cols;
-  const int nb1 = (int)std::max<long long>(1, std::min<long long>(((long long)n + 255) / 256, MAXB));
-  const int cb = (cols + 255) / 256;
-  const dim3 g2(cb, std::max(1, std::min(rows, MAXB / std::max(cb, 1))));
+  const int nb1 = fda_grid1d(rows, cols);
+  const dim3 g2 = lsqr_grid2d(rows, cols);
   hipLaunchKernelGGL(fda_mask_kernel, dim3(nb1), dim3(256), 0, stream, d_A, b);
   hipLaunchKernelGGL(fda_rhs_kernel, g2, dim3(256), 0, stream, d_A, b);
   SMRF_LAUNCH_CHECK();

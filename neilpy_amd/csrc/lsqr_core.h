@@ -1,8 +1,10 @@
 // SciPy's LSQR recurrence on the device, shared by the matrix-free solvers (springs.hip, fda.hip):
 // the scalars of scipy/sparse/linalg/_isolve/lsqr.py:324-555 (damp = 0) in float64 with no FMA
 // contraction, stepped by one-lane device code between the vector kernels, plus the fixed-tree
-// block reduction the vector kernels end in.  Everything lives in an anonymous namespace: each
-// translation unit gets its own copy.
+// block reduction the vector kernels end in, and the host driver of the iteration (lsqr_init_scalars,
+// lsqr_iterate).  A solver brings its struct of plane pointers (.part, .red, .sc), its set-up and
+// its two products.  Everything lives in an anonymous namespace: each translation unit gets its
+// own copy.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -15,6 +17,14 @@ namespace {
 #define SMRF_LSQR_MAXB 2048
 #endif
 constexpr int MAXB = SMRF_LSQR_MAXB;   // most blocks per vector kernel = partial sums per reduction
+
+inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// 2-D launch of the stencil kernels: 256 columns per block, rows strided over gridDim.y; at most MAXB blocks
+inline dim3 lsqr_grid2d(int rows, int cols) {
+  const int cb = (cols + 255) / 256;
+  return dim3(cb, std::max(1, std::min(rows, MAXB / std::max(cb, 1))));
+}
 
 struct Sc {
   double alfa, beta, inv_alfa, inv_beta;
@@ -105,6 +115,52 @@ __global__ __launch_bounds__(256) void reduce_kernel(const double* __restrict__ 
   for (int i = threadIdx.x; i < nb; i += 256) s += part[i];
   const double t = block_sum(s, red);
   if (threadIdx.x == 0) out[0] = t;
+}
+
+// block partials of two sums -> red[0], red[1]
+__global__ __launch_bounds__(256) void reduce2_kernel(const double* __restrict__ part, int nb, double* __restrict__ out) {
+  __shared__ double red[4];
+  __shared__ double red2[4];
+  double s0 = 0.0, s1 = 0.0;
+  for (int i = threadIdx.x; i < nb; i += 256) { s0 += part[i]; s1 += part[MAXB + i]; }
+  const double t0 = block_sum(s0, red);
+  const double t1 = block_sum(s1, red2);
+  if (threadIdx.x == 0) { out[0] = t0; out[1] = t1; }
+}
+
+// ---- the set-up's scalar steps: unknown count, |b|, the first alfa ------------------------------------------------
+// (sum: where the reduction left the step's sum; read where the step reads it)
+__device__ void count_step(Sc* sc, const double* sum) {
+  sc->nunk = (long long)*sum;
+  if (sc->iter_lim < 0) sc->iter_lim = 2 * sc->nunk;
+  if (sc->nunk == 0) sc->done = 1;
+}
+__device__ void bnorm_step(Sc* sc, const double* sum) {
+  const double bn = sqrt(*sum);
+  sc->bnorm = bn;
+  sc->beta = bn;
+  sc->beta_pos = bn > 0;
+  sc->inv_beta = bn > 0 ? 1 / bn : 1.0;
+  sc->alfa = 0.0;
+  sc->inv_alfa = 1.0;
+}
+__device__ void init_alfa_step(Sc* sc, const double* sum) {
+  if (sc->done) return;
+  const double a = sc->beta_pos ? sqrt(*sum) : 0.0;
+  sc->alfa = a;
+  sc->inv_alfa = a > 0 ? 1 / a : 1.0;
+  sc->rhobar = a;
+  sc->phibar = sc->beta;
+  if (a * sc->beta == 0) sc->done = 1;      // arnorm == 0: x = 0 is the answer (lsqr.py:386-390)
+}
+// one lane runs the STEPS (a sum of the flags) on the reduced sums: red[0], and red[1] = |b|^2 where the count rides along
+enum { LSQR_COUNT = 1, LSQR_BNORM = 2, LSQR_INIT_ALFA = 4 };
+template <int STEPS, typename B>   // B has .red and .sc
+__global__ void setup_scalar_kernel(const B b) {
+  static_assert(STEPS == LSQR_COUNT || STEPS == LSQR_BNORM || STEPS == (LSQR_COUNT | LSQR_BNORM) || STEPS == LSQR_INIT_ALFA);
+  if (STEPS & LSQR_COUNT) count_step(b.sc, b.red);
+  if (STEPS & LSQR_BNORM) bnorm_step(b.sc, b.red + (STEPS & LSQR_COUNT ? 1 : 0));
+  if (STEPS & LSQR_INIT_ALFA) init_alfa_step(b.sc, b.red);
 }
 
 __device__ void beta_step(Sc* sc, double sum_u) {
@@ -222,5 +278,101 @@ __global__ __launch_bounds__(256) void reduce_scalar_kernel(const B b, int nb) {
   }
 }
 
+// ---- the iteration since round 5 (single device and row bands): the x / w / dk steps ride in the pass that makes v ----
+// Iteration k was [atu: v_k, |v|^2] [alfa, rotation] [xwav: x_k, w_k, |dk|^2; u_{k+1}, |u|^2] [tests; beta]: 13 plane
+// touches (atu 3 reads + 1 write, xwav 5 + 4).  The rotation's rho, phi - hence t1 = phi / rho and 1 / rho - need only
+// rhobar and beta (rho_step), so they exist BEFORE the v pass, and that pass reads v_{k-1} and can read w_{k-2}:
+//   atuxw (iteration k):  w_{k-1} = v_{k-1} / alfa_{k-1} + t2_{k-1} w_{k-2}   (k = 1: w_0 = v_0 / alfa_0 - no w_init pass)
+//                         dk_k = w_{k-1} / rho_k, |dk|^2;   v_k = A^T u_k - beta_k v_{k-1}, |v|^2
+//                         k even: x_k = (x_{k-2} + t1_{k-1} w_{k-2}) + t1_k w_{k-1}  - both steps, from registers
+//   [alfa_k, rest of the rotation, tests_k]      av: u_{k+1} = A v_k - alfa_k u_k, |u|^2      [beta_{k+1}, rho_step]
+// x is read and written every SECOND iteration only: 12 touches instead of 13 (99 instead of 106 B per cell and iteration
+// with the springs' hole bytes), no separate w_init pass, w never initialised by the set-up.  A solve that stops at an odd k
+// leaves x one step behind; the scatter adds t1_k w_{k-1} (lsqr_x_pending; w still holds it: av and the next atuxw return at
+// once).  Every vector entry goes through the same operations on the same operands in the same order as before (x_k's two
+// roundings, w, dk, v), every partial sum runs over the same cells in the same order into the same slot: x, istop and
+// itn are bit-identical to round 4's four-launch form (tools/lsqr_ab.py against a round-4 build; the goldens' istop / itn).
+// The springs' row-band form runs the same two vector kernels as phases (PH_AV, PH_ATUXW) with the host's halo rows and
+// all-reduces between them: 12 plane touches per iteration where round 4's band phases (av, atu + |w|^2, xw) made 15, and
+// |dk|^2 is now SciPy's own sum over (w / rho)^2 (round 4's band form used |w|^2 / rho^2, a rounding apart).
+struct AtuxwSc {       // the scalars an atuxw pass reads
+  bool first, xupd, bpos;
+  double ib, ia, beta, t1, t1p, t2, ir;
+};
+__device__ __forceinline__ AtuxwSc atuxw_scalars(const Sc* sc) {
+  AtuxwSc q;
+  const long long itn = sc->itn;                           // k - 1
+  q.first = itn == 0; q.xupd = (itn & 1) != 0; q.bpos = sc->beta_pos != 0;
+  q.ib = sc->inv_beta; q.ia = sc->inv_alfa; q.beta = sc->beta;
+  q.t1 = sc->t1; q.t1p = sc->t1_prev; q.t2 = sc->t2; q.ir = sc->inv_rho;
+  return q;
+}
+// the x / w / dk step of unknown i; the caller sums dk^2 and, where q.bpos, makes v[i] = (A^T u_s)[i] - q.beta * vs
+struct LsqrXw { double vs, wn, dk; };
+__device__ __forceinline__ LsqrXw lsqr_xw_step(const AtuxwSc& q, double* x, const double* v, double* w, long long i) {
+  LsqrXw o;
+  o.vs = q.ia * v[i];
+  if (q.first) {
+    o.wn = o.vs;                                           // w_0 = v_0 / alfa_0 (lsqr.py:379)
+  } else {
+    const double wo = w[i];
+    o.wn = o.vs + q.t2 * wo;                               // w_{k-1} (lsqr.py:461, of the iteration before)
+    // x_{k-1} then x_k (lsqr.py:460), two roundings as before.  (Non-temporal accesses for x - touched every second
+    // iteration only - measured +1.2 % per iteration: profiles/r05_lsqr_split.md)
+    if (q.xupd) x[i] = (x[i] + q.t1p * wo) + q.t1 * o.wn;
+  }
+  w[i] = o.wn;
+  o.dk = q.ir * o.wn;                                      // lsqr.py:459
+  return o;
+}
+// the pending-x rule: a solve that stopped at an odd iteration k still owes x the step t1_k w_{k-1}; the scatter adds it
+__device__ __forceinline__ bool lsqr_x_pending(const Sc* sc) { return (sc->itn & 1) != 0; }
+
+// ---- host side -------------------------------------------------------------------------------------------------------
+// bare_products (smrf_fda_apply_f64): alfa = beta = 0 with unit scales, so the product kernels compute A v and A^T u alone
+inline int lsqr_init_scalars(Sc* d_sc, double atol, double btol, double conlim, int64_t iter_lim, hipStream_t st,
+                             bool bare_products = false) {
+  Sc h{};
+  h.atol = atol; h.btol = btol; h.ctol = conlim > 0 ? 1 / conlim : 0.0;
+  h.cs2 = -1.0; h.iter_lim = iter_lim;
+  if (bare_products) { h.inv_alfa = 1.0; h.inv_beta = 1.0; h.beta_pos = 1; }
+  SMRF_HIP_CHECK(hipMemcpyAsync(d_sc, &h, sizeof(h), hipMemcpyHostToDevice, st));
+  SMRF_HIP_CHECK(hipStreamSynchronize(st));   // h is a stack object
+  return SMRF_OK;
+}
+
+inline int lsqr_read_scalars(Sc& out, const Sc* d_sc, hipStream_t st) {
+  SMRF_HIP_CHECK(hipMemcpyAsync(&out, d_sc, sizeof(out), hipMemcpyDeviceToHost, st));
+  SMRF_HIP_CHECK(hipStreamSynchronize(st));
+  return SMRF_OK;
+}
+
+// The iteration after a solver's set-up (the first v and alfa are made): u_1, beta_1 + rho_step, then
+// iteration k = [atuxw: w_{k-1}, dk_k, (x), v_k] [alfa_k, rotation, tests_k] [av: u_{k+1}] [beta_{k+1}, rho_{k+1}]
+// until the device's stop flag is up.  The host reads the scalars back after 4, 8, ... chunk_cap iterations (the kernels
+// of a stopped solve return at once); out receives them as they are at the stop.
+template <typename B>   // B has .part and .sc
+int lsqr_iterate(const B& b, void (*atuxw)(B), void (*av)(B), dim3 grid, int nb, int chunk_cap, hipStream_t st, Sc& out) {
+  if (int rc = lsqr_read_scalars(out, b.sc, st)) return rc;
+  const long long lim = out.iter_lim;
+  if (!out.done && out.istop == 0 && out.itn < lim) {
+    hipLaunchKernelGGL(av, grid, dim3(256), 0, st, b);
+    hipLaunchKernelGGL((reduce_scalar_kernel<4, B>), dim3(1), dim3(256), 0, st, b, nb);
+    SMRF_LAUNCH_CHECK();
+  }
+  int chunk = 4;
+  while (!out.done && out.istop == 0 && out.itn < lim) {
+    for (int k = 0; k < chunk; ++k) {
+      hipLaunchKernelGGL(atuxw, grid, dim3(256), 0, st, b);
+      hipLaunchKernelGGL((reduce_scalar_kernel<3, B>), dim3(1), dim3(256), 0, st, b, nb);
+      hipLaunchKernelGGL(av, grid, dim3(256), 0, st, b);
+      hipLaunchKernelGGL((reduce_scalar_kernel<4, B>), dim3(1), dim3(256), 0, st, b, nb);
+    }
+    SMRF_LAUNCH_CHECK();
+    if (int rc = lsqr_read_scalars(out, b.sc, st)) return rc;
+    chunk = std::min(chunk_cap, chunk * 2);
+  }
+  return SMRF_OK;
+}
 
 }  // namespace

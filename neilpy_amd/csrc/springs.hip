@@ -14,7 +14,8 @@
 //     on every read, which reproduces scipy's "u = (1/beta) * u" rounding exactly and makes every
 //     kernel in-place safe (a thread only writes the entries it owns).
 // The scalar recurrence runs in one-lane kernels between the vector kernels, so an iteration needs
-// no host round trip; the host polls the stop flag every few iterations.
+// no host round trip; the host polls the stop flag every few iterations (lsqr_core.h: the scalar
+// steps, the x / w / dk step and the driver, shared with fda.hip).
 // Row-band form: every kernel works on rows [0, rows) of a band whose planes carry one halo row
 // above and one below (v and the hole mask below, uv above); the phase entry point lets the host
 // exchange those rows and all-reduce the one scalar between phases (neilpy_amd/sharded.py).  The
@@ -88,24 +89,6 @@ __global__ __launch_bounds__(256) void rhs_kernel(const double* __restrict__ A, 
   if (threadIdx.x == 0) b.part[blockIdx.y * gridDim.x + blockIdx.x] = t;
 }
 
-__global__ void s_count(const Band b) {
-  Sc* sc = b.sc;
-  sc->nunk = (long long)b.red[0];
-  if (sc->iter_lim < 0) sc->iter_lim = 2 * sc->nunk;
-  if (sc->nunk == 0) sc->done = 1;
-}
-
-__global__ void s_bnorm(const Band b) {
-  Sc* sc = b.sc;
-  const double bn = sqrt(b.red[0]);
-  sc->bnorm = bn;
-  sc->beta = bn;
-  sc->beta_pos = bn > 0;
-  sc->inv_beta = bn > 0 ? 1 / bn : 1.0;
-  sc->alfa = 0.0;
-  sc->inv_alfa = 1.0;
-}
-
 // ---- v = S^T u_s - beta * v_s  (u_s = inv_beta*u, v_s = inv_alfa*v), partial |v|^2: the set-up's first v ----------
 // (inside the iteration atuxw_kernel makes v together with the x / w / dk steps)
 __global__ __launch_bounds__(256) void atu_kernel(const Band b) {
@@ -151,45 +134,7 @@ __global__ __launch_bounds__(256) void atu_kernel(const Band b) {
   if (threadIdx.x == 0) b.part[SMRF_TILE_SLOT(tl)] = t;
 }
 
-// block partials of two sums -> red[0], red[1]
-__global__ __launch_bounds__(256) void reduce2_kernel(const double* __restrict__ part, int nb, double* __restrict__ out) {
-  __shared__ double red[4];
-  __shared__ double red2[4];
-  double s0 = 0.0, s1 = 0.0;
-  for (int i = threadIdx.x; i < nb; i += 256) { s0 += part[i]; s1 += part[MAXB + i]; }
-  const double t0 = block_sum(s0, red);
-  const double t1 = block_sum(s1, red2);
-  if (threadIdx.x == 0) { out[0] = t0; out[1] = t1; }
-}
-
-__global__ void s_init_alfa(const Band b) {
-  Sc* sc = b.sc;
-  if (sc->done) return;
-  const double a = sc->beta_pos ? sqrt(b.red[0]) : 0.0;
-  sc->alfa = a;
-  sc->inv_alfa = a > 0 ? 1 / a : 1.0;
-  sc->rhobar = a;
-  sc->phibar = sc->beta;
-  if (a * sc->beta == 0) sc->done = 1;      // arnorm == 0: x = 0 is the answer (lsqr.py:386-390)
-}
-
-// ---- the iteration since round 5 (single device and row bands): the x / w / dk steps ride in the pass that makes v ----
-// Iteration k was [atu: v_k, |v|^2] [alfa, rotation] [xwav: x_k, w_k, |dk|^2; u_{k+1}, |u|^2] [tests; beta]: 13 plane
-// touches (atu 3 reads + 1 write, xwav 5 + 4).  The rotation's rho, phi - hence t1 = phi / rho and 1 / rho - need only
-// rhobar and beta (lsqr_core.h: rho_step), so they exist BEFORE the v pass, and that pass reads v_{k-1} and can read w_{k-2}:
-//   atuxw (iteration k):  w_{k-1} = v_{k-1} / alfa_{k-1} + t2_{k-1} w_{k-2}   (k = 1: w_0 = v_0 / alfa_0 - no w_init pass)
-//                         dk_k = w_{k-1} / rho_k, |dk|^2;   v_k = S^T u_k - beta_k v_{k-1}, |v|^2
-//                         k even: x_k = (x_{k-2} + t1_{k-1} w_{k-2}) + t1_k w_{k-1}  - both steps, from registers
-//   [alfa_k, rest of the rotation, tests_k]      av2: u_{k+1} = S v_k - alfa_k u_k, |u|^2      [beta_{k+1}, rho_step]
-// x is read and written every SECOND iteration only: 12 touches instead of 13 (99 instead of 106 B per cell and iteration
-// with the hole bytes), no separate w_init pass, w never initialised by the set-up.  A solve that stops at an odd k leaves
-// x one step behind; scatter_kernel adds t1_k w_{k-1} (w still holds it: av2 and the next atuxw return at once).
-// Every vector entry goes through the same operations on the same operands in the same order as before (x_k's two
-// roundings, w, dk, v), every partial sum runs over the same cells in the same order into the same slot: x, istop and
-// itn are bit-identical to round 4's four-launch form (tools/lsqr_ab.py against a round-4 build; the goldens' istop / itn).
-// The row-band form runs the same two vector kernels as phases (PH_AV, PH_ATUXW) with the host's halo rows and all-reduces
-// between them: 12 plane touches per iteration where round 4's band phases (av, atu + |w|^2, xw) made 15, and |dk|^2 is now
-// SciPy's own sum over (w / rho)^2 (round 4's band form used |w|^2 / rho^2, a rounding apart).
+// ---- the iteration's v pass with the x / w / dk steps riding in it (lsqr_core.h: lsqr_xw_step has the derivation) ----
 __global__ __launch_bounds__(256) void atuxw_kernel(const Band b) {
   __shared__ double red[4];
   __shared__ double red2[4];
@@ -198,10 +143,7 @@ __global__ __launch_bounds__(256) void atuxw_kernel(const Band b) {
   const int rows = b.rows, cols = b.cols;
   const long long ld = b.ld;
   const LsqrTile tl = lsqr_tile(b.nxcd);
-  const long long itn = sc->itn;                           // k - 1
-  const bool first = itn == 0, xupd = (itn & 1) != 0, bpos = sc->beta_pos != 0;
-  const double ib = sc->inv_beta, ia = sc->inv_alfa, beta = sc->beta;
-  const double t1 = sc->t1, t1p = sc->t1_prev, t2 = sc->t2, ir = sc->inv_rho;
+  const AtuxwSc q = atuxw_scalars(sc);
   double s = 0.0, sd = 0.0;
   {
     const int c = tl.x * 256 + (int)threadIdx.x;
@@ -213,27 +155,15 @@ __global__ __launch_bounds__(256) void atuxw_kernel(const Band b) {
         const int rn = r + (int)gridDim.y;
         const uint8_t hn = rn < rows ? b.hole[(long long)rn * ld + c] : (uint8_t)0;   // one row of the walk ahead (atu_kernel)
         if (h) {
-          const double vs = ia * b.v[i];
-          double wn;
-          if (first) {
-            wn = vs;                                       // w_0 = v_0 / alfa_0 (lsqr.py:379)
-          } else {
-            const double wo = b.w[i];
-            wn = vs + t2 * wo;                             // w_{k-1} (lsqr.py:461, of the iteration before)
-            // x_{k-1} then x_k (lsqr.py:460), two roundings as before.  (Non-temporal accesses for x - touched every second
-            // iteration only - measured +1.2 % per iteration: profiles/r05_lsqr_split.md)
-            if (xupd) b.x[i] = (b.x[i] + t1p * wo) + t1 * wn;
-          }
-          b.w[i] = wn;
-          const double dk = ir * wn;                       // lsqr.py:459
-          sd += dk * dk;
-          if (bpos) {                                      // beta == 0: v and alfa stay (lsqr.py:434-441)
+          const LsqrXw o = lsqr_xw_step(q, b.x, b.v, b.w, i);
+          sd += o.dk * o.dk;
+          if (q.bpos) {                                    // beta == 0: v and alfa stay (lsqr.py:434-441)
             double y = 0.0;
-            if (r > 0 || b.has_above) y = y - ib * b.uv[i - ld];
-            if (c > 0) y = y - ib * b.uh[i - 1];
-            if (c + 1 < cols) y = y + ib * b.uh[i];
-            if (r + 1 < rows || b.has_below) y = y + ib * b.uv[i];
-            const double nv = y - beta * vs;
+            if (r > 0 || b.has_above) y = y - q.ib * b.uv[i - ld];
+            if (c > 0) y = y - q.ib * b.uh[i - 1];
+            if (c + 1 < cols) y = y + q.ib * b.uh[i];
+            if (r + 1 < rows || b.has_below) y = y + q.ib * b.uv[i];
+            const double nv = y - q.beta * o.vs;
             b.v[i] = nv;
             s += nv * nv;
           }
@@ -361,29 +291,12 @@ __global__ __launch_bounds__(256) void setup_kernel(const double* __restrict__ A
   }
 }
 
-__global__ void s_count_bnorm(const Band b) {             // red[0] = holes, red[1] = |b|^2: s_count then s_bnorm
-  Sc* sc = b.sc;
-  sc->nunk = (long long)b.red[0];
-  if (sc->iter_lim < 0) sc->iter_lim = 2 * sc->nunk;
-  if (sc->nunk == 0) sc->done = 1;
-  const double bn = sqrt(b.red[1]);
-  sc->bnorm = bn;
-  sc->beta = bn;
-  sc->beta_pos = bn > 0;
-  sc->inv_beta = bn > 0 ? 1 / bn : 1.0;
-  sc->alfa = 0.0;
-  sc->inv_alfa = 1.0;
-}
-
-// pend: the solve stopped at an odd iteration k - x still lacks t1_k w_{k-1} (atuxw_kernel)
 __global__ __launch_bounds__(256) void scatter_kernel(double* __restrict__ A, const Band b) {
-  const bool pend = (b.sc->itn & 1) != 0;
+  const bool pend = lsqr_x_pending(b.sc);
   const double t1 = b.sc->t1;
   SMRF_FOR_CELLS_P(b.rows, b.cols, b.ld)
     if (b.hole[i]) A[(long long)r * b.cols + c] = pend ? b.x[i] + t1 * b.w[i] : b.x[i];
 }
-
-size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // workspace carve-up shared by the single-device solver and the band phases.
 // offsets (bytes): x, v, w, uh, uv (first ALLOCATED row = halo above), hole, abelow, part, red, sc
@@ -452,27 +365,20 @@ enum Phase {
   PH_SCATTER = 10,    // A[hole] = x (+ t1 w when the solve stopped at an odd iteration)
 };
 
-// 2-D launch of the stencil kernels: 256 columns per block, rows strided over gridDim.y; at most MAXB blocks
-dim3 grid2d(const Band& b) {
-  const int cb = (b.cols + 255) / 256;
-  const int rb = std::max(1, std::min(b.rows, MAXB / std::max(cb, 1)));
-  return dim3(cb, std::max(rb, 1));
-}
-
 int run_phase(int phase, double* A, const Band& b, hipStream_t st) {
-  const dim3 g2 = grid2d(b);
+  const dim3 g2 = lsqr_grid2d(b.rows, b.cols);
   const int nb2 = (int)(g2.x * g2.y);
   auto reduce = [&](int count) { hipLaunchKernelGGL(reduce_kernel, dim3(1), dim3(256), 0, st, (const double*)b.part, count, b.red); };
   switch (phase) {
     case PH_MASK: hipLaunchKernelGGL(mask_kernel, g2, dim3(256), 0, st, (const double*)A, b); reduce(nb2); break;
     case PH_RHS:
-      hipLaunchKernelGGL(s_count, dim3(1), dim3(1), 0, st, b);
+      hipLaunchKernelGGL((setup_scalar_kernel<LSQR_COUNT, Band>), dim3(1), dim3(1), 0, st, b);
       hipLaunchKernelGGL(rhs_kernel, g2, dim3(256), 0, st, (const double*)A, b);
       reduce(nb2);
       break;
-    case PH_BNORM: hipLaunchKernelGGL(s_bnorm, dim3(1), dim3(1), 0, st, b); break;
+    case PH_BNORM: hipLaunchKernelGGL((setup_scalar_kernel<LSQR_BNORM, Band>), dim3(1), dim3(1), 0, st, b); break;
     case PH_ATU: hipLaunchKernelGGL(atu_kernel, g2, dim3(256), 0, st, b); reduce(nb2); break;
-    case PH_INIT_ALFA: hipLaunchKernelGGL(s_init_alfa, dim3(1), dim3(1), 0, st, b); break;   // (w_0 is made by the first atuxw pass)
+    case PH_INIT_ALFA: hipLaunchKernelGGL((setup_scalar_kernel<LSQR_INIT_ALFA, Band>), dim3(1), dim3(1), 0, st, b); break;   // (w_0 is made by the first atuxw pass)
     case PH_AV: hipLaunchKernelGGL(av2_kernel, g2, dim3(256), 0, st, b); reduce(nb2); break;
     case PH_BETA_RHO: hipLaunchKernelGGL(s_beta_rho, dim3(1), dim3(1), 0, st, b); break;
     case PH_ATUXW:
@@ -484,15 +390,6 @@ int run_phase(int phase, double* A, const Band& b, hipStream_t st) {
     default: return smrf_fail(SMRF_E_ARG, "unknown springs phase %d", phase);
   }
   SMRF_LAUNCH_CHECK();
-  return SMRF_OK;
-}
-
-int init_scalars(const Band& b, double atol, double btol, double conlim, int64_t iter_lim, hipStream_t st) {
-  Sc h{};
-  h.atol = atol; h.btol = btol; h.ctol = conlim > 0 ? 1 / conlim : 0.0;
-  h.cs2 = -1.0; h.iter_lim = iter_lim;
-  SMRF_HIP_CHECK(hipMemcpyAsync(b.sc, &h, sizeof(h), hipMemcpyHostToDevice, st));
-  SMRF_HIP_CHECK(hipStreamSynchronize(st));   // h is a stack object
   return SMRF_OK;
 }
 
@@ -511,40 +408,19 @@ int smrf_springs_lsqr_f64(double* d_A, int rows, int cols, double atol, double b
   if (!d_workspace || workspace_bytes < smrf_springs_workspace_bytes(rows, cols))
     return smrf_fail(SMRF_E_WORKSPACE, "springs workspace too small");
   const Band b = band_of(d_workspace, rows, cols, padded_pitch(cols), 0, 0);
-  if (int rc = init_scalars(b, atol, btol, conlim, iter_lim, stream)) return rc;
-  const dim3 g2 = grid2d(b);
+  if (int rc = lsqr_init_scalars(b.sc, atol, btol, conlim, iter_lim, stream)) return rc;
+  const dim3 g2 = lsqr_grid2d(b.rows, b.cols);
   const int nb = (int)(g2.x * g2.y);
   // set-up: one plane pass (mask + right-hand side + counts), the first v = S^T u, alfa; then u_1 and beta_1 + rho_step
   hipLaunchKernelGGL(setup_kernel, g2, dim3(256), 0, stream, (const double*)d_A, b);
   hipLaunchKernelGGL(reduce2_kernel, dim3(1), dim3(256), 0, stream, (const double*)b.part, nb, b.red);
-  hipLaunchKernelGGL(s_count_bnorm, dim3(1), dim3(1), 0, stream, b);
+  hipLaunchKernelGGL((setup_scalar_kernel<LSQR_COUNT | LSQR_BNORM, Band>), dim3(1), dim3(1), 0, stream, b);
   hipLaunchKernelGGL(atu_kernel, g2, dim3(256), 0, stream, b);
   hipLaunchKernelGGL(reduce_kernel, dim3(1), dim3(256), 0, stream, (const double*)b.part, nb, b.red);
-  hipLaunchKernelGGL(s_init_alfa, dim3(1), dim3(1), 0, stream, b);
+  hipLaunchKernelGGL((setup_scalar_kernel<LSQR_INIT_ALFA, Band>), dim3(1), dim3(1), 0, stream, b);
   SMRF_LAUNCH_CHECK();
   Sc out{};
-  SMRF_HIP_CHECK(hipMemcpyAsync(&out, b.sc, sizeof(out), hipMemcpyDeviceToHost, stream));
-  SMRF_HIP_CHECK(hipStreamSynchronize(stream));
-  const long long lim = out.iter_lim;
-  if (!out.done && out.istop == 0 && out.itn < lim) {
-    hipLaunchKernelGGL(av2_kernel, g2, dim3(256), 0, stream, b);
-    hipLaunchKernelGGL((reduce_scalar_kernel<4, Band>), dim3(1), dim3(256), 0, stream, b, nb);
-    SMRF_LAUNCH_CHECK();
-  }
-  int chunk = 4;
-  while (!out.done && out.istop == 0 && out.itn < lim) {
-    for (int k = 0; k < chunk; ++k) {
-      // Iteration k = [w_{k-1}, dk_k, (x), v_k] [alfa_k, rotation, tests_k] [u_{k+1}] [beta_{k+1}, rho_{k+1}]  (atuxw_kernel)
-      hipLaunchKernelGGL(atuxw_kernel, g2, dim3(256), 0, stream, b);
-      hipLaunchKernelGGL((reduce_scalar_kernel<3, Band>), dim3(1), dim3(256), 0, stream, b, nb);
-      hipLaunchKernelGGL(av2_kernel, g2, dim3(256), 0, stream, b);
-      hipLaunchKernelGGL((reduce_scalar_kernel<4, Band>), dim3(1), dim3(256), 0, stream, b, nb);
-    }
-    SMRF_LAUNCH_CHECK();
-    SMRF_HIP_CHECK(hipMemcpyAsync(&out, b.sc, sizeof(out), hipMemcpyDeviceToHost, stream));
-    SMRF_HIP_CHECK(hipStreamSynchronize(stream));
-    chunk = std::min(32, chunk * 2);
-  }
+  if (int rc = lsqr_iterate(b, atuxw_kernel, av2_kernel, g2, nb, 32, stream, out)) return rc;
   if (out.nunk > 0) {
     hipLaunchKernelGGL(scatter_kernel, g2, dim3(256), 0, stream, d_A, b);
     SMRF_LAUNCH_CHECK();
@@ -578,7 +454,7 @@ int smrf_springs_band_begin(int rows_local, int cols, double atol, double btol, 
     return smrf_fail(SMRF_E_WORKSPACE, "springs band workspace too small");
   const Band b = band_of(d_workspace, rows_local, cols, padded_pitch(cols), 0, 0);
   SMRF_HIP_CHECK(hipMemsetAsync(d_workspace, 0, layout_of(rows_local, cols, padded_pitch(cols)).total, (hipStream_t)stream));
-  return init_scalars(b, atol, btol, conlim, iter_lim, (hipStream_t)stream);
+  return lsqr_init_scalars(b.sc, atol, btol, conlim, iter_lim, (hipStream_t)stream);
 }
 
 int smrf_springs_band_phase(int phase, double* d_A_band, int rows_local, int cols, int has_above, int has_below,
@@ -595,8 +471,7 @@ int smrf_springs_band_status(const void* d_workspace, int rows_local, int cols, 
   if (!d_workspace || !h_istop || !h_itn || !h_done) return smrf_fail(SMRF_E_ARG, "null pointer");
   const Band b = band_of(const_cast<void*>(d_workspace), rows_local, cols, padded_pitch(cols), 0, 0);
   Sc out{};
-  SMRF_HIP_CHECK(hipMemcpyAsync(&out, b.sc, sizeof(out), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  SMRF_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+  if (int rc = lsqr_read_scalars(out, b.sc, (hipStream_t)stream)) return rc;
   *h_istop = out.istop;
   *h_itn = (int64_t)out.itn;
   *h_done = out.done || out.istop != 0 || out.itn >= out.iter_lim;

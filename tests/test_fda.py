@@ -153,3 +153,60 @@ def test_hip_operator_equals_explicit_system(gpu_device, shape, frac, seed):
     assert np.max(np.abs(rhs[k] - b), initial=0.0) <= 1e-13 * scale
     assert np.max(np.abs(Av[k] - want_Av), initial=0.0) <= 1e-13 * max(1.0, float(np.abs(want_Av).max(initial=0.0)))
     assert np.max(np.abs(Atu[nan_list] - want_Atu), initial=0.0) <= 1e-13 * max(1.0, float(np.abs(want_Atu).max(initial=0.0)))
+
+
+_FIXED = {}
+
+
+def _fixed_reference(shape, frac, seed, K):
+    """SciPy's iterate after exactly K iterations, its last step and the bar: all from the reference alone."""
+    key = (shape, frac, seed, K)
+    if key not in _FIXED:
+        from scipy.sparse.linalg import lsqr
+        rng = np.random.default_rng(seed)
+        A = rng.normal(100.0, 20.0, size=shape)
+        A[rng.random(shape) < frac] = np.nan
+        a, b, nan_list = orc.fda_system(A)
+        run = lambda a_, b_, k: lsqr(a_, b_, atol=0, btol=0, conlim=0, iter_lim=k)   # noqa: E731
+        ref = run(a, b, K)
+        assert (ref[1], ref[2]) == (7, K)
+        xmax = float(np.abs(ref[0]).max())
+        p = np.random.default_rng(1000 + seed).permutation(a.shape[0])
+        moved = float(np.abs(run(a[p], b[p], K)[0] - ref[0]).max()) / xmax
+        tol = max(1e-13, 100.0 * moved)
+        step = float(np.abs(ref[0] - run(a, b, K - 1)[0]).max()) / xmax
+        for v in (A, nan_list, ref[0]):
+            v.setflags(write=False)
+        _FIXED[key] = A, nan_list, ref[0], xmax, tol, step
+    return _FIXED[key]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K", (5, 6))
+@pytest.mark.parametrize("shape,frac,seed", [((9, 7), .3, 1), ((40, 33), .5, 2), ((64, 300), .2, 3)])
+def test_hip_pending_x_at_fixed_iteration(gpu_device, shape, frac, seed, K):
+    """The x step left pending at an odd stop: x is written every second iteration, so a solve cut at an odd K owes
+    t1_K w_{K-1} in the scatter, and one cut at an even K owes nothing.  The solver is stopped after exactly K iterations
+    (all tolerances 0, iter_lim = K) and compared with SciPy stopped the same way.  The bar is 100 x the movement of
+    SciPy's own iterate at that K under a row permutation of the system (relative to max |x|, floor 1e-13; the factor
+    covers the device's different, fixed, summation trees); SciPy's last step is at least 1000 x larger, so a dropped or
+    doubled pending step cannot pass."""
+    import ctypes as C
+    import torch
+    from neilpy_amd import _lib
+    lib = _lib.load()
+    A, nan_list, want, xmax, tol, step = _fixed_reference(shape, frac, seed, K)
+    assert step >= 1000.0 * tol
+    m, n = shape
+    A_d = torch.from_numpy(A.copy()).to(gpu_device)
+    nbytes = lib.smrf_fda_workspace_bytes(m, n)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=gpu_device)
+    istop, itn, nunk = C.c_int(0), C.c_int64(0), C.c_int64(0)
+    _lib.check(lib.smrf_fda_lsqr_f64(C.c_void_p(A_d.data_ptr()), m, n, 0.0, 0.0, 0.0, K, C.byref(istop), C.byref(itn),
+                                     C.byref(nunk), C.c_void_p(ws.data_ptr()), nbytes,
+                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    assert (istop.value, itn.value, nunk.value) == (7, K, nan_list.size)
+    got = A_d.cpu().numpy().ravel()[nan_list]
+    diff = float(np.abs(got - want).max()) / xmax
+    print("fda fixed K=%d %s: device vs SciPy %.3g, bar %.3g, SciPy's last step %.3g" % (K, shape, diff, tol, step))
+    assert diff <= tol

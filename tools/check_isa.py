@@ -6,7 +6,7 @@ inline-asm reads and staging stores).  Exit code 1 if either is found.
 
     python tools/check_isa.py [-j 8]
 
---dump DIR also compiles incero.hip and writes DIR/manifest.txt, one line per kernel: symbol, VGPRs, SGPRs, scratch and LDS
+--dump DIR also compiles incero.hip, springs.hip and fda.hip and writes DIR/manifest.txt, one line per kernel: symbol, VGPRs, SGPRs, scratch and LDS
 bytes, sha256 of its instructions.  `diff` of two trees' manifests shows whether a change reached the generated code.
 """
 import argparse
@@ -102,12 +102,13 @@ def manifest(text):
 
 
 DEFS = []
+UNITS = {-1: "chain", -2: "incero", -3: "springs", -4: "fda"}
 
 
 def one(job):
     part, f64, tmp = job
     if part < 0:                                           # chain.hip: the chained / table-free launches (both dtypes in one
-        name = "chain" if part == -1 else "incero"         # unit); incero.hip (--dump only): the incremental erosion
+        name = UNITS[part]                                 # unit); --dump only: incero.hip and the two LSQR solvers
         out = os.path.join(tmp, name + ".s")
         cmd = [hipcc()] + [f for f in FLAGS if f != "-fPIC"] + DEFS + ["--offload-device-only", "-S", os.path.join(CSRC, name + ".hip"),
                                                                "-o", out]
@@ -146,7 +147,7 @@ def main():
     a = ap.parse_args()
     DEFS[:] = [d for d in a.defs.split() if d]
     with tempfile.TemporaryDirectory() as tmp:
-        jobs = [(p, f, tmp) for f in ((0,) if a.f32_only else (0, 1)) for p in range(RING_PARTS)] + [(-1, 0, tmp)] + ([(-2, 0, tmp)] if a.dump else [])
+        jobs = [(p, f, tmp) for f in ((0,) if a.f32_only else (0, 1)) for p in range(RING_PARTS)] + [(-1, 0, tmp)] + ([(p, 0, tmp) for p in (-2, -3, -4)] if a.dump else [])
         with ThreadPoolExecutor(max_workers=a.j) as ex:
             res = list(ex.map(one, jobs))
     if a.dump:
@@ -157,7 +158,7 @@ def main():
     for part, f64, bad, _ in res:
         for b in bad:
             n += 1
-            print("%s: %s" % ("incero" if part == -2 else "chain" if part < 0 else "ring_%s_p%d" % ("f64" if f64 else "f32", part), b))
+            print("%s: %s" % (UNITS[part] if part < 0 else "ring_%s_p%d" % ("f64" if f64 else "f32", part), b))
     print("%d finding(s) in %d translation units" % (n, len(res)))
     return 1 if n else 0
 

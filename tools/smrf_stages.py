@@ -57,10 +57,10 @@ def run(points=20_000_000, extent=8192.0, windows=18, cellsize=1.0, seed=20241, 
 
     def lsqr(name):
         if warm:                                           # (the solver fills Zmin in place: its warm-up run gets a copy)
-            api._springs_device(Zmin.clone(), name)
+            api._lsqr_device(Zmin.clone(), "springs", name)
         torch.cuda.synchronize()
         t = time.perf_counter()
-        api._springs_device(Zmin, name)
+        api._lsqr_device(Zmin, "springs", name)
         torch.cuda.synchronize()
         stages[name + "_ms"] = (time.perf_counter() - t) * 1e3
         st = dict(api.last_stats[name])
