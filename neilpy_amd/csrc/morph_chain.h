@@ -447,38 +447,22 @@ int chain_launch(const ChainArgs<T>& a_in, hipStream_t stream) {
   using C = ChainCfg<NP, R0, R1, R2, R3>;
   using T2 = typename Vec2<T>::type;
   constexpr size_t LDS = (size_t)C::CELLS * sizeof(T2);
-  auto kern = chain_kernel<T, NP, OCC, R0, R1, R2, R3>;
-  static int resident_of[64] = {0};
-  int dev = 0;
-  SMRF_HIP_CHECK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return smrf_fail(SMRF_E_UNSUPPORTED, "device index %d out of range", dev);
-  int resident = __atomic_load_n(&resident_of[dev], __ATOMIC_ACQUIRE);
-  if (resident == 0) {
-    if (LDS > 48 * 1024)
-      SMRF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)LDS));
-    int nb = 0;
-    SMRF_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kern), C::TW, LDS));
-    resident = std::max(1, nb);
-    __atomic_store_n(&resident_of[dev], resident, __ATOMIC_RELEASE);
-    if (smrf_sw().ring_debug)
-      fprintf(stderr, "smrf chain: R=%d,%d,%d,%d %s NP=%d LDS=%zu, %d workgroups/CU resident\n", R0, R1, R2, R3,
-              sizeof(T) == 4 ? "f32" : "f64", NP, LDS, resident);
-  }
+  constexpr auto kern = chain_kernel<T, NP, OCC, R0, R1, R2, R3>;
+  int resident;
+  bool first;
+  if (int rc = smrf_resident<kern>(C::TW, LDS, resident, first)) return rc;
+  if (first && smrf_sw().ring_debug)
+    fprintf(stderr, "smrf chain: R=%d,%d,%d,%d %s NP=%d LDS=%zu, %d workgroups/CU resident\n", R0, R1, R2, R3,
+            sizeof(T) == 4 ? "f32" : "f64", NP, LDS, resident);
   ChainArgs<T> a = a_in;
   const int strips = (a.cols + C::TWO - 1) / C::TWO;
-  if (a.seg <= 0) {
-    // Asks for three workgroups per resident slot (round 3: chain 4, 5 on 16384^2 1.17 -> 0.87 ms - the counters showed 2.4
-    // waves per SIMD where 4 were expected: with what round 5's per-workgroup timestamps show, that was a one-round launch's
-    // tail - its youngest workgroups end 3 % per residency class behind - and, at the time, a second, nearly empty round
-    // whenever the segment count rounded up).  smrf_pick_nseg (seg_rule.h) weighs the three rounds against the best single
-    // round and takes the cheaper: three on the benchmark raster, one below ~10^8 cells.
-    const int rounds = smrf_sw().chain_rounds;
-    const int nseg = smrf_pick_nseg(a.out_rows, strips, resident, rounds, 2 * C::S, C::ROWS, std::max(32, 4 * C::S), smrf_sw().seg_rule);
-    int seg = (a.out_rows + nseg - 1) / nseg;
-    a.seg = seg;
-  }
-  a.seg = ((a.seg + C::ROWS - 1) / C::ROWS) * C::ROWS;
+  // Asks for three workgroups per resident slot (round 3: chain 4, 5 on 16384^2 1.17 -> 0.87 ms - the counters showed 2.4
+  // waves per SIMD where 4 were expected: with what round 5's per-workgroup timestamps show, that was a one-round launch's
+  // tail - its youngest workgroups end 3 % per residency class behind - and, at the time, a second, nearly empty round
+  // whenever the segment count rounded up).  smrf_pick_nseg (seg_rule.h) weighs the three rounds against the best single
+  // round and takes the cheaper: three on the benchmark raster, one below ~10^8 cells.
+  a.seg = smrf_seg_len(a.out_rows, strips, resident, smrf_sw().chain_rounds, 2 * C::S, C::ROWS, std::max(32, 4 * C::S),
+                       smrf_sw().seg_rule, a.seg);
   dim3 grid(strips, (a.out_rows + a.seg - 1) / a.seg);
   hipLaunchKernelGGL(kern, grid, dim3(C::TW), LDS, stream, a);
   SMRF_LAUNCH_CHECK();

@@ -265,35 +265,19 @@ int fused_launch(const DiskArgs<T>& a_in, hipStream_t stream) {
   constexpr int NP = fused_np<T>(R);
   using C = RingCfg<T, R, TW, NP>;
   constexpr size_t LDS = 2 * C::LDS_BYTES;
-  auto kern = fused_open_kernel<T, R, TW, NP>;
-  static int resident_of[64] = {0};
-  int dev = 0;
-  SMRF_HIP_CHECK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return smrf_fail(SMRF_E_UNSUPPORTED, "device index %d out of range", dev);
-  int resident = __atomic_load_n(&resident_of[dev], __ATOMIC_ACQUIRE);
-  if (resident == 0) {
-    if (LDS > 48 * 1024)
-      SMRF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)LDS));
-    int nb = 0;
-    SMRF_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kern), TW, LDS));
-    resident = std::max(1, nb);
-    __atomic_store_n(&resident_of[dev], resident, __ATOMIC_RELEASE);
-    if (smrf_sw().ring_debug)
-      fprintf(stderr, "smrf fused: R=%d %s NP=%d LDS=%zu, %d workgroups/CU resident\n", R, sizeof(T) == 4 ? "f32" : "f64", NP,
-              LDS, resident);
-  }
+  constexpr auto kern = fused_open_kernel<T, R, TW, NP>;
+  int resident;
+  bool first;
+  if (int rc = smrf_resident<kern>(TW, LDS, resident, first)) return rc;
+  if (first && smrf_sw().ring_debug)
+    fprintf(stderr, "smrf fused: R=%d %s NP=%d LDS=%zu, %d workgroups/CU resident\n", R, sizeof(T) == 4 ? "f32" : "f64", NP,
+            LDS, resident);
   DiskArgs<T> a = a_in;
   constexpr int TWO = TW - 2 * R;
   const int strips = (a.cols + TWO - 1) / TWO;
-  if (a.seg <= 0) {
-    const int rounds = smrf_sw().fused_rounds;
-    // one round: every workgroup resident; a segment re-reads 4R warm-up rows (smrf_pick_nseg, seg_rule.h)
-    const int nseg = smrf_pick_nseg(a.out_rows, strips, resident, rounds, 4 * R, C::ROWS, std::max(32, 8 * R), smrf_sw().seg_rule);
-    int seg = (a.out_rows + nseg - 1) / nseg;
-    a.seg = seg;
-  }
-  a.seg = ((a.seg + C::ROWS - 1) / C::ROWS) * C::ROWS;
+  // one round: every workgroup resident; a segment re-reads 4R warm-up rows (smrf_pick_nseg, seg_rule.h)
+  a.seg = smrf_seg_len(a.out_rows, strips, resident, smrf_sw().fused_rounds, 4 * R, C::ROWS, std::max(32, 8 * R),
+                       smrf_sw().seg_rule, a.seg);
   dim3 grid(strips, (a.out_rows + a.seg - 1) / a.seg);
   hipLaunchKernelGGL(kern, grid, dim3(TW), LDS, stream, a);
   SMRF_LAUNCH_CHECK();

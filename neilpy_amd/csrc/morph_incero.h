@@ -189,29 +189,17 @@ __global__ __launch_bounds__(256) void inc_erode_kernel(const IncEroArgs<T> a) {
 template <typename T, int R>
 int inc_erode_launch(const IncEroArgs<T>& a_in, hipStream_t stream) {
   using C = IncEroCfg<R>;
-  auto kern = inc_erode_kernel<T, R>;
-  static int resident_of[64] = {0};                       // workgroups one CU holds, per device
-  int dev = 0;
-  SMRF_HIP_CHECK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return smrf_fail(SMRF_E_UNSUPPORTED, "device index %d out of range", dev);
-  int resident = __atomic_load_n(&resident_of[dev], __ATOMIC_ACQUIRE);
-  if (resident == 0) {
-    int nb = 0;
-    SMRF_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kern), C::TW, 0));
-    resident = std::max(1, nb);
-    __atomic_store_n(&resident_of[dev], resident, __ATOMIC_RELEASE);
-    if (smrf_sw().ring_debug)
-      fprintf(stderr, "smrf inc erode: R=%d pairs=%d reach=%d LDS=%zu, %d workgroups/CU resident\n", R, C::N, C::DY,
-              C::LDS_CELLS * 2 * sizeof(T), resident);
-  }
+  constexpr auto kern = inc_erode_kernel<T, R>;
+  int resident;
+  bool first;
+  if (int rc = smrf_resident<kern>(C::TW, 0, resident, first)) return rc;   // (its LDS is static)
+  if (first && smrf_sw().ring_debug)
+    fprintf(stderr, "smrf inc erode: R=%d pairs=%d reach=%d LDS=%zu, %d workgroups/CU resident\n", R, C::N, C::DY,
+            C::LDS_CELLS * 2 * sizeof(T), resident);
   IncEroArgs<T> a = a_in;
   const int strips = (a.cols + C::TW - 1) / C::TW;
-  if (a.seg <= 0) {
-    const int nseg = smrf_pick_nseg(a.rows, strips, resident, smrf_sw().ring_rounds, 2 * C::DY + C::DELTA, C::ROWS,
-                                    std::max(32, 4 * C::DY), smrf_sw().seg_rule);
-    a.seg = (a.rows + nseg - 1) / nseg;
-  }
-  a.seg = ((a.seg + C::ROWS - 1) / C::ROWS) * C::ROWS;
+  a.seg = smrf_seg_len(a.rows, strips, resident, smrf_sw().ring_rounds, 2 * C::DY + C::DELTA, C::ROWS, std::max(32, 4 * C::DY),
+                       smrf_sw().seg_rule, a.seg);
   a.plain_tiles = smrf_sw().xcd_remap ? 0 : 1;
   dim3 grid(strips, (a.rows + a.seg - 1) / a.seg);
   hipLaunchKernelGGL(kern, grid, dim3(C::TW), 0, stream, a);

@@ -62,7 +62,7 @@
 #define SMRF_RING_XCD_REMAP 1   // XCD-aware tile placement (smrf_xcd_tile); 0: workgroup (x, y) takes tile (x, y)
 #endif
 #ifndef SMRF_RING_SLOPE_DEFAULT
-#define SMRF_RING_SLOPE_DEFAULT 60  // permille of segment length per residency class (ring_launch_np); SMRF_RING_SLOPE overrides
+#define SMRF_RING_SLOPE_DEFAULT 60  // permille of segment length per residency class (smrf_ring_plan, seg_rule.h); SMRF_RING_SLOPE overrides
 #endif
 #ifndef SMRF_RING_OCC_DROP
 #define SMRF_RING_OCC_DROP 0   // tuning builds: run every radius one occupancy step below the estimate
@@ -1209,7 +1209,7 @@ void ring_kernel(const DiskArgs<T> a) {
   T2* const L = reinterpret_cast<T2*>(smrf_lds);         // [NP][NLEV][WP] of {row A, row B}
 
   const int tid = threadIdx.x;
-  int bx, by;   // the general branch: equal segments only (ring_launch_np's residency classes count on `by` growing with the dispatch id)
+  int bx, by;   // the general branch: equal segments only (smrf_ring_plan's residency classes count on `by` growing with the dispatch id)
   smrf_xcd_tile(!SMRF_RING_XCD_REMAP || a.plain_tiles, [&] { return a.seg_cls == 0; }, bx, by);
 #ifdef SMRF_RING_DBG_CLOCK   // timing experiment only: the shader clock this workgroup ran at, left in the output's first two cells
   const unsigned long long dbg_t0 = __builtin_amdgcn_s_memtime(), dbg_q0 = __builtin_amdgcn_s_memrealtime();
@@ -1220,7 +1220,7 @@ void ring_kernel(const DiskArgs<T> a) {
   const int x0 = bx * TW;
   const int x = x0 + tid;
   int ys, ye;                                            // global output rows [ys, ye)
-  if (a.seg_cls > 0) {                                   // segments of unequal length (ring_launch_np: residency classes)
+  if (a.seg_cls > 0) {                                   // segments of unequal length (smrf_ring_plan: residency classes)
     int cls = 0;
     for (int c = 1; c < a.seg_cls; ++c) cls += by >= a.seg_first[c] ? 1 : 0;
     ys = a.out_row0 + a.seg_row0[cls] + (by - a.seg_first[cls]) * a.seg_len[cls];
@@ -1547,109 +1547,40 @@ template <typename T, int R, bool DIL, int NP>
 int ring_launch_np(const DiskArgs<T>& a_in, hipStream_t stream, bool probe_only, int* seg_if_launched) {
   constexpr int TW = kRingTW;
   using C = RingCfg<T, R, TW, NP>;
-  auto kern = ring_kernel<T, R, DIL, TW, NP>;
-  // workgroups one CU really holds (registers + LDS), per device: the attribute below is per device too
-  static int resident_of[64] = {0};
-  int dev = 0;
-  SMRF_HIP_CHECK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return smrf_fail(SMRF_E_UNSUPPORTED, "device index %d out of range", dev);
-  int resident = __atomic_load_n(&resident_of[dev], __ATOMIC_ACQUIRE);   // host threads may launch one radius at once
-  if (resident == 0) {
-    if (C::LDS_BYTES > 48 * 1024)
-      SMRF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES));
-    int nb = 0;
-    SMRF_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kern), TW,
-                                                              C::LDS_BYTES));
-    resident = std::max(1, nb);
-    __atomic_store_n(&resident_of[dev], resident, __ATOMIC_RELEASE);
-    if (smrf_sw().ring_debug)
-      fprintf(stderr, "smrf ring: R=%d %s%s NP=%d G=%d%s LDS=%zu built for %d waves/SIMD, %d workgroups/CU resident\n", R,
-              sizeof(T) == 4 ? "f32" : "f64", DIL ? " dilate" : " erode", NP, C::G, C::INPLACE ? " in-place" : "", C::LDS_BYTES,
-              C::OCC, resident);
-  }
+  constexpr auto kern = ring_kernel<T, R, DIL, TW, NP>;
+  int resident;
+  bool first;
+  if (int rc = smrf_resident<kern>(TW, C::LDS_BYTES, resident, first)) return rc;
+  if (first && smrf_sw().ring_debug)
+    fprintf(stderr, "smrf ring: R=%d %s%s NP=%d G=%d%s LDS=%zu built for %d waves/SIMD, %d workgroups/CU resident\n", R,
+            sizeof(T) == 4 ? "f32" : "f64", DIL ? " dilate" : " erode", NP, C::G, C::INPLACE ? " in-place" : "", C::LDS_BYTES,
+            C::OCC, resident);
   DiskArgs<T> a = a_in;
   const int strips = (a.cols + TW - 1) / TW;
-  if (a.seg <= 0) {
-    // output rows per workgroup: one round (every workgroup resident at once, the longest segments, the fewest re-read
-    // halo rows) is the fastest from radius 20 up and as fast as any below (tools/ring_tune.py cur@SMRF_RING_ROUNDS=n);
-    // how many rows of segments that round holds - all slots on a large raster, the CUs k times over on a small one -
-    // is smrf_pick_nseg's cost model (seg_rule.h)
-    const int rounds = smrf_sw().ring_rounds;
-    const int nseg = smrf_pick_nseg(a.out_rows, strips, resident, rounds, 2 * R, C::ROWS, std::max(32, 4 * R), smrf_sw().seg_rule);
-    int seg = (a.out_rows + nseg - 1) / nseg;
-    a.seg = seg;
-  }
-  a.seg = ((a.seg + C::ROWS - 1) / C::ROWS) * C::ROWS;
-  const int seg_equal = a.seg;
-  int grid_y = (a.out_rows + a.seg - 1) / a.seg;
-  // Segments of unequal length.  All workgroups of a one-round launch start within ~1 us, but they do not run at one speed:
-  // a CU's SIMDs issue oldest wave first, so the workgroup that reached a CU first finishes first - measured per workgroup
-  // (tools/experiments/ring_tails.py, profiles/r05_segment_balance.md): the k-th workgroup of a CU takes 5-9 % longer than the
-  // (k-1)-th at every radius, the launch lasts as long as the youngest, and the workgroups are resident for only 0.87-0.90 of
-  // it on average.  Workgroups are dealt to the CUs in dispatch order, 256 at a time (8 XCDs x 32 CUs), and ring_kernel's tile
-  // mapping makes `by` grow with the dispatch id: segment `by` is of residency class (by * strips + strips / 2) / 256 (where most
-  // of its workgroups are), and the segments of class c get 1 + slope * ((classes - 1) / 2 - c) times the mean length.  Any
-  // segmentation gives the same bits.
-  a.seg_cls = 0;
-  a.plain_tiles = smrf_sw().xcd_remap ? 0 : 1;
-  {
-    // Measured (profiles/r05_segment_balance.md): -1.4 ... -2.1 % of the 16384^2 step at 60 permille per class (40 ... 100 are
-    // within 0.3 % of it), nothing for fp64 (its classes differ by 3 %), and -1 ... +1 % where the classes do not fall on
-    // whole rows of segments (strips does not divide 256) - so the built-in slope is for fp32 rasters whose strips do;
-    // SMRF_RING_SLOPE=n asks for n whatever the shape.
-    const int slope_env = smrf_sw().ring_slope;
-    const int slope = slope_env >= 0 ? slope_env : (sizeof(T) == 4 && 256 % strips == 0 ? SMRF_RING_SLOPE_DEFAULT : 0);
-    const bool one_round = a_in.seg <= 0 && smrf_sw().ring_rounds == 1;
-    const auto cls_of = [&](int by) { return std::min(7, (int)(((long long)by * strips + strips / 2) / 256)); };
-    const int ncls = cls_of(grid_y - 1) + 1;
-    if (slope > 0 && one_round && strips <= 256 && ncls >= 2) {
-      int n[8] = {0};
-      for (int by = 0; by < grid_y; ++by) n[cls_of(by)]++;
-      double wsum = 0.0, w[8];
-      for (int c = 0; c < ncls; ++c) {
-        w[c] = 1.0 + 1e-3 * slope * (0.5 * (ncls - 1) - c);
-        wsum += w[c] * n[c];
-      }
-      const double base = (double)a.out_rows / wsum;
-      int first = 0, row0 = 0, longest = 0;
-      bool ok = true;
-      for (int c = 0; c < 8; ++c) {
-        int len = C::ROWS;
-        if (c < ncls) {
-          len = std::max(1, (int)(base * w[c] / C::ROWS + 0.999)) * C::ROWS;      // up to a multiple of the batch
-          ok = ok && n[c] > 0 && 2 * len >= std::max(32, 4 * R);
-        }
-        a.seg_first[c] = c < ncls ? first : grid_y;
-        a.seg_row0[c] = row0;
-        a.seg_len[c] = len;
-        if (c < ncls) {
-          first += n[c];
-          row0 += n[c] * len;
-          longest = std::max(longest, len);
-        }
-      }
-      if (ok && row0 >= a.out_rows) {
-        a.seg_cls = ncls;
-        a.seg = longest;                                                    // what the span clamp below looks at
-      }
-    }
-  }
+  // the built-in slope of the unequal segments is for fp32 rasters whose strip count divides 256 (smrf_ring_plan says why);
+  // SMRF_RING_SLOPE=n asks for n whatever the shape
+  const int slope_env = smrf_sw().ring_slope;
+  const int slope = slope_env >= 0 ? slope_env : (sizeof(T) == 4 && 256 % strips == 0 ? SMRF_RING_SLOPE_DEFAULT : 0);
+  int max_rows = 0;
   if constexpr (ring_buf_on<T, R, TW, NP>()) {
     // buffer addressing: a workgroup's row offsets are 32-bit (and not range-checked by the hardware): keep the span of
     // a segment (its rows + warm-up + one batch) below 2 GiB
     const long long rowb = (long long)a.ld * (long long)sizeof(T);
-    const long long max_rows = ((1ll << 31) - 1) / rowb - (4 * R + 4 * C::ROWS);
-    if (max_rows < C::ROWS) return smrf_fail(SMRF_E_UNSUPPORTED, "raster rows of %lld bytes are too long for this build", rowb);
-    if (a.seg > max_rows) {
-      a.seg_cls = 0;
-      a.seg = std::min(seg_equal, (int)(max_rows / C::ROWS) * C::ROWS);
-    }
+    const long long most = ((1ll << 31) - 1) / rowb - (4 * R + 4 * C::ROWS);
+    if (most < C::ROWS) return smrf_fail(SMRF_E_UNSUPPORTED, "raster rows of %lld bytes are too long for this build", rowb);
+    max_rows = (int)most;
   }
-  if (a.seg_cls == 0) grid_y = (a.out_rows + a.seg - 1) / a.seg;
-  if (seg_if_launched) *seg_if_launched = a.seg_cls ? seg_equal : a.seg;   // (the dual rule looks at the mean length)
+  const SmrfRingPlan p = smrf_ring_plan(a.out_rows, strips, R, C::ROWS, resident, smrf_sw().ring_rounds, smrf_sw().seg_rule,
+                                        slope, a_in.seg, max_rows);
+  a.seg = p.seg;
+  a.seg_cls = p.seg_cls;
+  std::copy(p.seg_first, p.seg_first + 8, a.seg_first);
+  std::copy(p.seg_row0, p.seg_row0 + 8, a.seg_row0);
+  std::copy(p.seg_len, p.seg_len + 8, a.seg_len);
+  a.plain_tiles = smrf_sw().xcd_remap ? 0 : 1;
+  if (seg_if_launched) *seg_if_launched = p.seg_cls ? p.seg_equal : p.seg;   // (the dual rule looks at the mean length)
   if (probe_only) return SMRF_OK;
-  dim3 grid(strips, grid_y);
+  dim3 grid(strips, p.grid_y);
   hipLaunchKernelGGL(kern, grid, dim3(TW), C::LDS_BYTES, stream, a);
   SMRF_LAUNCH_CHECK();
   return SMRF_OK;

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 
 #include "smrf_hip.h"
 
@@ -97,7 +98,29 @@ inline float smrf_float_below(double t) {
   return f;
 }
 
-#include "seg_rule.h"   // smrf_pick_nseg: how a launch is cut into row segments (plain C++: tests/test_host_logic.py compiles it)
+#include "seg_rule.h"   // smrf_seg_len, smrf_ring_plan: how a launch is cut into row segments (plain C++: tests/test_host_logic.py compiles it)
+
+// Workgroups of `Kern` (`block` threads, `lds` bytes of dynamic LDS) one CU really holds (registers + LDS), asked once per
+// kernel and device - the attribute that allows more than 48 KB of dynamic LDS is per device too - and at least 1.
+// `first`: this call asked (the launchers print their SMRF_RING_DEBUG geometry line then).
+template <auto Kern>
+int smrf_resident(int block, size_t lds, int& resident, bool& first) {
+  static int resident_of[64] = {0};
+  int dev = 0;
+  SMRF_HIP_CHECK(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64) return smrf_fail(SMRF_E_UNSUPPORTED, "device index %d out of range", dev);
+  resident = __atomic_load_n(&resident_of[dev], __ATOMIC_ACQUIRE);   // host threads may launch one kernel at once
+  first = resident == 0;
+  if (first) {
+    const void* const kern = reinterpret_cast<const void*>(Kern);
+    if (lds > 48 * 1024) SMRF_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int nb = 0;
+    SMRF_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, block, lds));
+    resident = std::max(1, nb);
+    __atomic_store_n(&resident_of[dev], resident, __ATOMIC_RELEASE);
+  }
+  return SMRF_OK;
+}
 
 // arguments of one disk erosion / dilation pass over a row band (see smrf_hip.h)
 template <typename T>
@@ -120,7 +143,7 @@ struct DiskArgs {
   int dense;          // flag step writes EVERY mask / when byte (0 included): the planes need no clearing first
   // segments of unequal length (ring kernels, round 5): seg_cls = number of classes (0: every segment is `seg` rows); class c
   // holds the segments seg_first[c] .. seg_first[c + 1] - 1, each seg_len[c] rows, the first at out_row0 + seg_row0[c].
-  // See ring_launch_np.
+  // Filled by ring_launch_np from smrf_ring_plan (seg_rule.h).
   int seg_cls;
   int seg_first[8], seg_row0[8], seg_len[8];
   int plain_tiles;    // 1: workgroup (x, y) takes tile (x, y) (SMRF_XCD_REMAP=0, A/B runs); 0: the XCD-aware placement of the kernel

@@ -328,3 +328,30 @@ def test_segment_count_rounds_down(nz, gpu_device, monkeypatch):
         assert torch.equal(nz.progressive_filter(Zs, win, 1, .15), want_s), rule
         for r, w in e.items():
             assert torch.equal(nz.erosion(Z, radius=r, impl=1), w), (rule, r)
+
+
+def test_launch_geometry_is_asked_once_per_kernel():
+    """csrc/smrf_common.h smrf_resident: the ring, fused, chained and incremental-erosion launchers ask once per kernel
+    (and device) how many of its workgroups a CU holds, and print their SMRF_RING_DEBUG geometry line then.  A fresh
+    process runs the same 16 windows twice through all four launchers (tests/launch_geometry_child.py): every kind of line
+    is there, none twice (one cache per kernel, filled by the first launch), every instance is resident at least once,
+    and the second run - all of it on cached geometry - gives the first one's mask."""
+    import os
+    import re
+    import subprocess
+    import sys
+    from conftest import ROOT
+    env = {k: v for k, v in os.environ.items() if not k.startswith("SMRF_")}
+    env.update(SMRF_RING_DEBUG="1", SMRF_FUSED="2", SMRF_ERO_INC="2")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "launch_geometry_child.py")], capture_output=True, text=True,
+                       timeout=300, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stderr.splitlines() if ln.startswith("smrf ")]
+    for kind in ("smrf ring:", "smrf fused:", "smrf chain:", "smrf inc erode:"):
+        assert any(ln.startswith(kind) for ln in lines), (kind, lines)
+    assert len(set(lines)) == len(lines), sorted(ln for ln in lines if lines.count(ln) > 1)
+    for ln in lines:
+        m = re.search(r"(\d+) workgroups/CU resident$", ln)
+        assert m and int(m.group(1)) >= 1, ln
+    out = r.stdout.split()
+    assert out[0] == "masks" and out[1] == out[2] and int(out[3]) > 0, r.stdout

@@ -209,6 +209,122 @@ def test_segment_rule_picks(tmp_path):
         assert nseg == 1 or nseg * strips <= resident * 256, (c, nseg)
 
 
+_RING_PLAN_CPP = r'''
+#include <cstdio>
+#include <vector>
+#include "seg_rule.h"
+// ring_kernel's decoding of the plan (csrc/morph_ring.h, "int ys, ye;  // global output rows [ys, ye)"), with out_row0 = 0
+static void rows_of(const SmrfRingPlan& p, int out_rows, int by, int& ys, int& ye) {
+  if (p.seg_cls > 0) {
+    int cls = 0;
+    for (int c = 1; c < p.seg_cls; ++c) cls += by >= p.seg_first[c] ? 1 : 0;
+    ys = p.seg_row0[cls] + (by - p.seg_first[cls]) * p.seg_len[cls];
+    ye = std::min(out_rows, ys + p.seg_len[cls]);
+  } else {
+    ys = by * p.seg;
+    ye = std::min(out_rows, ys + p.seg);
+  }
+}
+int main() {   // out_rows strips radius batch resident rounds rule slope forced max_rows
+  int v[10];
+  while (std::scanf("%d %d %d %d %d %d %d %d %d %d", v, v + 1, v + 2, v + 3, v + 4, v + 5, v + 6, v + 7, v + 8, v + 9) == 10) {
+    const SmrfRingPlan p = smrf_ring_plan(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9]);
+    std::vector<int> seen(v[0], 0);
+    long wrong = 0;                                        // rows not written exactly once, or written outside the raster
+    for (int by = 0; by < p.grid_y; ++by) {
+      int ys, ye;
+      rows_of(p, v[0], by, ys, ye);
+      if (ys < 0) ++wrong;
+      for (int y = ys < 0 ? 0 : ys; y < ye; ++y) ++seen[y];
+    }
+    for (int y = 0; y < v[0]; ++y) wrong += seen[y] != 1;
+    std::printf("%ld %d %d %d %d", wrong, p.seg, p.grid_y, p.seg_cls, p.seg_equal);
+    for (int c = 0; c < 8; ++c) std::printf(" %d", p.seg_first[c]);
+    for (int c = 0; c < 8; ++c) std::printf(" %d", p.seg_row0[c]);
+    for (int c = 0; c < 8; ++c) std::printf(" %d", p.seg_len[c]);
+    std::printf("\n");
+  }
+  return 0;
+}
+'''
+
+
+def test_ring_plan_covers_every_row_once(tmp_path):
+    """csrc/seg_rule.h smrf_ring_plan: where the output rows of a ring pass go - equal segments, or residency classes of
+    unequal length (profiles/r05_segment_balance.md section 3), the fall-backs to equal segments and the 2 GiB span clamp.
+    A row that no segment takes would be a silent hole in the output, so the plan is decoded here the way ring_kernel
+    decodes it and every row must be taken exactly once, whatever the inputs; a handful of plans are pinned in full (the
+    values are those of the launcher's arithmetic before it moved here)."""
+    import os
+    import random
+    import subprocess
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = tmp_path / "plan.cpp"
+    src.write_text(_RING_PLAN_CPP)
+    exe = tmp_path / "plan"
+    r = subprocess.run(["g++", "-O1", "-I", os.path.join(ROOT, "neilpy_amd", "csrc"), str(src), "-o", str(exe)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-1500:]
+
+    def plans(cases):
+        out = subprocess.run([str(exe)], input="\n".join(" ".join(str(v) for v in c) for c in cases) + "\n",
+                             capture_output=True, text=True, check=True).stdout.splitlines()
+        assert len(out) == len(cases)
+        res = []
+        for ln in out:
+            v = [int(t) for t in ln.split()]
+            res.append(dict(wrong=v[0], seg=v[1], grid_y=v[2], cls=v[3], equal=v[4], first=v[5:13], row0=v[13:21], len=v[21:29]))
+        return res
+
+    #        rows  strips  R batch resident rounds rule slope forced max_rows
+    pinned = [((16384, 64, 50, 4, 3, 1, 0, 60, 0, 0),        # the benchmark's shape: 3 classes of 4 segments
+               dict(seg=1448, grid_y=12, cls=3, equal=1368, first=[0, 4, 8, 12, 12, 12, 12, 12],
+                    row0=[0, 5792, 11264, 16400, 16400, 16400, 16400, 16400], len=[1448, 1368, 1284, 4, 4, 4, 4, 4])),
+              ((30000, 24, 20, 6, 4, 1, 0, 100, 0, 0),       # classes that do not fall on whole rows of segments
+               dict(seg=822, grid_y=42, cls=4, equal=720, first=[0, 11, 21, 32, 42, 42, 42, 42],
+                    row0=[0, 9042, 16542, 24000, 30060, 30060, 30060, 30060], len=[822, 750, 678, 606, 6, 6, 6, 6])),
+              ((8193, 33, 50, 4, 2, 1, 1, 60, 0, 0),         # rule 1's second, nearly empty round; a slope forced on 33 strips
+               dict(seg=528, grid_y=16, cls=2, equal=516, first=[0, 8, 16, 16, 16, 16, 16, 16],
+                    row0=[0, 4224, 8224, 8224, 8224, 8224, 8224, 8224], len=[528, 500, 4, 4, 4, 4, 4, 4])),
+              ((8193, 33, 50, 4, 2, 1, 0, -1, 0, 0), dict(seg=548, grid_y=15, cls=0, equal=548)),        # no slope: equal
+              ((5526, 16, 58, 4, 6, 1, 0, 300, 0, 0), dict(seg=116, grid_y=48, cls=0, equal=116)),       # class 2 below 2R rows: refused
+              ((16384, 64, 50, 4, 3, 1, 0, 60, 0, 1000), dict(seg=1000, grid_y=17, cls=0, equal=1368)),  # the span clamp
+              ((16384, 64, 50, 4, 3, 1, 0, 60, 136, 0), dict(seg=136, grid_y=121, cls=0, equal=136)),    # a forced length
+              ((16384, 64, 50, 4, 3, 2, 0, 60, 0, 0), dict(seg=1368, grid_y=12, cls=0, equal=1368)),     # two rounds: equal
+              ((3, 1, 4, 4, 4, 1, 0, 60, 0, 0), dict(seg=4, grid_y=1, cls=0, equal=4))]                  # fewer rows than a batch
+    for (c, want), got in zip(pinned, plans([c for c, _ in pinned])):
+        assert got["wrong"] == 0 and {k: got[k] for k in want} == want, (c, got)
+
+    rnd = random.Random(11)
+    cases = []
+    for _ in range(6000):
+        batch = rnd.choice((2, 4, 6))
+        # (weighted towards what a launch usually gets - one round, no forced length, no clamp - so that the unequal
+        # segments are reached often enough: the share is asserted below)
+        cases.append((rnd.randint(1, 40000), rnd.randint(1, 300), rnd.randint(1, 64), batch, rnd.randint(1, 8),
+                      rnd.choice((1, 1, 1, 1, 1, 1, 1, 2)), 0, rnd.choice((0, 40, 60, 100, 300)),
+                      rnd.choice((0, 0, 0, 0, 0, 0, 0, 0, 0, 8, 50, 136)),
+                      rnd.choice((0, 0, 0, 0, 0, rnd.randint(batch, 600)))))
+    unequal = 0
+    for c, p in zip(cases, plans(cases)):
+        rows, strips, radius, batch, resident, rounds, rule, slope, forced, max_rows = c
+        assert p["wrong"] == 0, (c, p)                                       # every output row exactly once
+        assert p["seg"] > 0 and p["seg"] % batch == 0 and p["equal"] > 0 and p["equal"] % batch == 0, (c, p)
+        assert max_rows == 0 or p["seg"] <= max_rows, (c, p)
+        if p["cls"] == 0:
+            assert p["grid_y"] == (rows + p["seg"] - 1) // p["seg"], (c, p)
+            continue
+        unequal += 1
+        n = p["cls"]
+        assert 2 <= n <= 8 and rounds == 1 and forced == 0 and slope > 0 and strips <= 256, (c, p)
+        first = p["first"] + [p["grid_y"]]
+        assert first[0] == 0 and all(first[k] < first[k + 1] for k in range(n)), (c, p)      # every class in use has segments
+        assert all(first[k] == p["grid_y"] for k in range(n, 9)), (c, p)                     # ... and the last ends at grid_y
+        assert all(l > 0 and l % batch == 0 for l in p["len"]), (c, p)
+        assert p["seg"] == max(p["len"][:n]), (c, p)
+    assert 4 * unequal >= len(cases), unequal
+
+
 def test_power_sampler_reads_hwmon_files(tmp_path):
     """tools/gpu_power.py (bench.py's roofline.power): the sampler thread reads power1_input (uW) / freq1_input (Hz) of a
     hwmon directory and reports median / max watts and the median clock of a time span; without the files it says so
