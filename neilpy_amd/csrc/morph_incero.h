@@ -13,9 +13,10 @@
 // batch is prefetched into registers with coalesced loads while this one is consumed; the staging area is double
 // buffered: one barrier per batch.  Every input row is SCATTERED into the accumulators of the output rows it reaches:
 // slot s of a register ring of 2 reach + 8 slots belongs to output row (first input row of the batch) - reach + s, the
-// cell pair (dy, +-dx) of input row j updates slot j - dy + reach with one tied v_min3 - all indices compile-time, a
-// slot that receives nothing costs nothing - and the ring turns by 8 slots per batch.  The 8 rows a batch completes take
-// the cross of e_{R-1} (five loads per cell, issued before the batch's LDS phase) and are stored.  No scratch.
+// cell pair (dy, +-dx) of input row j updates slot j - dy + reach with one v_min3 - all indices compile-time, a slot that
+// receives nothing costs one move - and the ring turns by 8 slots per batch inside those updates (IncEroCfg::Plan).  The 8
+// rows a batch completes take the cross of e_{R-1} (five loads per cell, issued before the batch's LDS phase and before
+// the prefetch, so that the waits for them leave the prefetch in flight) and are stored one batch late.  No scratch.
 #pragma once
 #include "morph_ring.h"
 
@@ -53,6 +54,42 @@ struct IncEroCfg {
   static constexpr int gsize(int g) { const int n = NJ - g * G; return n < 0 ? 0 : n > G ? G : n; }
   static constexpr int dy(int k) { return kEroInc[R].p[k].dy; }
   static constexpr int dx(int k) { return kEroInc[R].p[k].dx; }
+  // job j = (row pair j / N, cell pair j % N) updates the ring slots slot(j) (row A of its pair) and slot(j) + 1 (row B)
+  static constexpr int slot(int j) { return 2 * (j / N) - dy(j % N) + DY; }
+  // A batch runs its jobs by ascending slot (seq[i] = the i-th job), so that slot s receives its first update - the one
+  // that reads what slot s + ROWS held - before slot s + ROWS receives its own and overwrites that: the two values never
+  // live at once, and the ring turns in place.  first[s] = the position in seq of the first job that updates slot s, NJ if
+  // the batch leaves the slot alone.
+  struct Plan { short seq[NJ > 0 ? NJ : 1], first[NACC]; };
+  static constexpr Plan make_plan() {
+    Plan pl{};
+    int n = 0;
+    for (int s = 0; s < NACC; ++s) {
+      pl.first[s] = NJ;
+      for (int j = 0; j < NJ; ++j)
+        if (slot(j) == s) pl.seq[n++] = (short)j;
+    }
+    for (int i = NJ - 1; i >= 0; --i) pl.first[slot(pl.seq[i])] = pl.first[slot(pl.seq[i]) + 1] = (short)i;
+    return pl;
+  }
+  static constexpr Plan plan = make_plan();
+  // every job is run once, every slot a batch updates has exactly one first update, and slot s has it before slot s + ROWS
+  // (tests/test_gpu_incero_overlap.py states the same in Python from ero_inc.inc)
+  static constexpr bool plan_ok() {
+    int seen[NJ > 0 ? NJ : 1] = {};
+    for (int i = 0; i < NJ; ++i) ++seen[plan.seq[i]];
+    for (int j = 0; j < NJ; ++j)
+      if (seen[j] != 1) return false;
+    for (int s = 0; s < NACC; ++s) {
+      int firsts = 0, touches = 0;
+      for (int i = 0; i < NJ; ++i)
+        for (int h = 0; h < 2; ++h)
+          if (slot(plan.seq[i]) + h == s) { ++touches; firsts += plan.first[s] == i; }
+      if (firsts != (touches > 0)) return false;
+      if (s + ROWS < NACC && plan.first[s] < NJ && plan.first[s + ROWS] < NJ && plan.first[s] >= plan.first[s + ROWS]) return false;
+    }
+    return true;
+  }
   // the row loop starts DELTA rows early so that the 8 rows a batch completes never straddle the segment's first row
   static constexpr int DELTA = (ROWS - (2 * DY) % ROWS) % ROWS;
   static constexpr int LDS_CELLS = N > 0 ? 2 * NP * W : 1;
@@ -83,6 +120,7 @@ __global__ __launch_bounds__(256) void inc_erode_kernel(const IncEroArgs<T> a) {
 #pragma unroll
   for (int i = 0; i < NACC; ++i) acc[i] = ident<T>(false);
 
+  static_assert(C::plan_ok(), "the batch plan");
   int o0 = ys - 2 * DY - C::DELTA;                        // first of the 8 output rows the next batch completes
   const int nb = (ye - o0 + ROWS - 1) / ROWS;
   RowFold rf(o0 + DY, a.rows);                            // tracks the NEXT batch to prefetch (its first input row)
@@ -94,28 +132,43 @@ __global__ __launch_bounds__(256) void inc_erode_kernel(const IncEroArgs<T> a) {
       const T* rb = a.last + (long long)rf.at(2 * p + 1) * a.ld;
 #pragma unroll
       for (int i = 0; i < NPOS; ++i)
-        if (i < NPOS - 1 || act[i]) { pf[p][i].x = ra[cpos[i]]; pf[p][i].y = rb[cpos[i]]; }
-    }
+        { pf[p][i].x = ra[cpos[i]]; pf[p][i].y = rb[cpos[i]]; }   // (a lane without a cell in the last position re-reads
+    }                                                               // its first: no branch, so the waits can count the loads)
     rf.advance(ROWS);
   };
   if constexpr (N > 0) prefetch();
 
+  // The order of a batch's memory operations is what lets its loads overlap the LDS phase AND the epilogue: the counter of
+  // outstanding vector-memory operations retires in order, so a wait for one load also waits for everything issued
+  // before it.  Per batch, after the barrier: (1) the stores of the PREVIOUS batch's rows (outv: deferred, so that no wait
+  // for a load ever covers a fresh store), (2) the cross loads of this batch's rows, (3) the prefetch of the next batch -
+  // unconditionally (past the last batch it re-reads folded rows nobody uses): a prefetch under a branch would make the
+  // epilogue's waits assume the path without it and drain it.  The epilogue then waits for (2) only and leaves the NP * NPOS * 2
+  // loads of (3) in flight until the next batch's staging, where nothing younger is outstanding.
+  T outv[ROWS];
+  auto store_rows = [&](int ob) {                         // the 8 rows from output row ob
+#pragma unroll
+    for (int j = 0; j < ROWS; ++j)
+      if (ob + j < ye && x < a.cols) smrf_store_out(a.out + (long long)(ob + j) * a.ld + x, outv[j], a.nt);
+  };
   for (int b = 0; b < nb; ++b, o0 += ROWS) {
     const unsigned lds_b = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(L + (b & 1) * NP * W + tid);
     if constexpr (N > 0) {
       // stage the prefetched batch.  The other half of L may still be read by a slower wave (batch b - 1): it is not touched
-      // before the NEXT barrier, which that wave reaches only after it has finished reading.
+      // before the NEXT barrier, which that wave reaches only after it has finished reading.  No branch here either: a lane
+      // without a cell in the last position writes the copy of its first cell (prefetch) over that cell, so every path
+      // waits for every prefetched register and none is left pending for the load that next writes it.
 #pragma unroll
       for (int p = 0; p < NP; ++p)
 #pragma unroll
         for (int i = 0; i < NPOS; ++i)
-          if (i < NPOS - 1 || act[i]) lds_write2(lds_b + (unsigned)((p * W + i * TW) * (int)sizeof(T2)), pf[p][i]);
+          lds_write2(lds_b + (unsigned)((p * W + (i < NPOS - 1 || act[i] ? i * TW : 0)) * (int)sizeof(T2)), pf[p][i]);
       lds_wait<0>();
       __syncthreads();
-      if (b + 1 < nb) prefetch();
     }
+    if (o0 - ROWS >= ys) store_rows(o0 - ROWS);            // (whole batches: DELTA)
     // the cross of e_{R-1} for the rows this batch completes: loads issued now, used after the LDS phase
-    const bool store = o0 >= ys;                          // (whole batches: DELTA)
+    const bool store = o0 >= ys;
     T ec[ROWS + 2], el[ROWS], er[ROWS];
     if (store) {
       RowFold rfe(o0 - 1, a.rows);
@@ -127,20 +180,41 @@ __global__ __launch_bounds__(256) void inc_erode_kernel(const IncEroArgs<T> a) {
       }
     }
     if constexpr (N > 0) {
-      // scatter: job J = (row pair p, cell pair k) reads {rowA, rowB} at columns x - dx and x + dx and updates the slots of output
-      // rows 2p - dy and 2p + 1 - dy.  Groups of G jobs, the next group's reads in flight while this one's min3 issue.
+      __builtin_amdgcn_sched_barrier(0);                  // the cross loads stay older than the prefetch
+      prefetch();
+      __builtin_amdgcn_sched_barrier(0);
+      // the ring turns by one batch WITHOUT moves: slot s continues what slot s + 8 held, and the first update a slot receives
+      // in a batch reads that value and writes the slot's own register (untied); the later ones are tied.  Only a slot
+      // that receives nothing is copied; a new-born slot (the top 8) starts from its first update's two cells.
+      T old[NACC];
+#pragma unroll
+      for (int s = 0; s < NACC; ++s) old[s] = acc[s];
+      [&]<int... S>(std::integer_sequence<int, S...>) {
+        (([&] {
+           if constexpr (C::plan.first[S] == C::NJ) acc[S] = S + ROWS < NACC ? old[S + ROWS] : ident<T>(false);
+         }()),
+         ...);
+      }(std::make_integer_sequence<int, NACC>{});
+      // scatter: job (row pair p, cell pair k) reads {rowA, rowB} at columns x - dx and x + dx and updates the slots of output
+      // rows 2p - dy and 2p + 1 - dy.  Groups of G jobs in the plan's order, the next group's reads in flight while this one's
+      // min3 issue.
       T2 rd[2 * G][2];
-      auto issue = [&]<int J>(std::integral_constant<int, J>) {
-        constexpr int p = J / N, k = J % N;
+      auto issue = [&]<int I>(std::integral_constant<int, I>) {
+        constexpr int J = C::plan.seq[I], p = J / N, k = J % N;
         constexpr int offl = (p * W + DY - C::dx(k)) * (int)sizeof(T2), offr = (p * W + DY + C::dx(k)) * (int)sizeof(T2);
-        rd[J % (2 * G)][0] = lds_read2<offl>(lds_b, T());
-        rd[J % (2 * G)][1] = lds_read2<offr>(lds_b, T());
+        rd[I % (2 * G)][0] = lds_read2<offl>(lds_b, T());
+        rd[I % (2 * G)][1] = lds_read2<offr>(lds_b, T());
       };
-      auto apply = [&]<int J>(std::integral_constant<int, J>) {
-        constexpr int p = J / N, k = J % N, s = 2 * p - C::dy(k) + DY;
-        static_assert(s >= 0 && s + 1 < NACC, "slot outside the ring");
-        op3_acc<false>(acc[s], rd[J % (2 * G)][0].x, rd[J % (2 * G)][1].x);
-        op3_acc<false>(acc[s + 1], rd[J % (2 * G)][0].y, rd[J % (2 * G)][1].y);
+      auto update = [&]<int S, int I>(std::integral_constant<int, S>, std::integral_constant<int, I>, const T& l, const T& r) {
+        static_assert(S >= 0 && S < NACC, "slot outside the ring");
+        if constexpr (C::plan.first[S] != I) op3_acc<false>(acc[S], l, r);
+        else if constexpr (S + ROWS < NACC) acc[S] = op3<false>(old[S + ROWS], l, r);
+        else acc[S] = op2<false>(l, r);
+      };
+      auto apply = [&]<int I>(std::integral_constant<int, I> i) {
+        constexpr int s = C::slot(C::plan.seq[I]);
+        update(std::integral_constant<int, s>{}, i, rd[I % (2 * G)][0].x, rd[I % (2 * G)][1].x);
+        update(std::integral_constant<int, s + 1>{}, i, rd[I % (2 * G)][0].y, rd[I % (2 * G)][1].y);
       };
       auto issue_group = [&]<int Gi>(std::integral_constant<int, Gi>) {
         [&]<int... I>(std::integer_sequence<int, I...>) {
@@ -172,18 +246,11 @@ __global__ __launch_bounds__(256) void inc_erode_kernel(const IncEroArgs<T> a) {
         T m = op3<false>(ec[j + 1], el[j], er[j]);
         m = op3<false>(m, ec[j], ec[j + 2]);
         if constexpr (N > 0) m = op2<false>(m, acc[j]);
-        const int o = o0 + j;
-        if (o < ye && x < a.cols) smrf_store_out(a.out + (long long)o * a.ld + x, m, a.nt);
+        outv[j] = m;
       }
     }
-    if constexpr (N > 0) {
-      // the ring turns by one batch
-#pragma unroll
-      for (int s = 0; s < NACC - ROWS; ++s) acc[s] = acc[s + ROWS];
-#pragma unroll
-      for (int s = NACC - ROWS; s < NACC; ++s) acc[s] = ident<T>(false);
-    }
   }
+  if (o0 - ROWS >= ys) store_rows(o0 - ROWS);              // the last batch's rows
 }
 
 template <typename T, int R>

@@ -21,12 +21,15 @@ for d in ("pmc1", "pmc2", "pmc3"):
             k = r["Kernel_Name"]
             m = (re.search(r"(ring_kernel)<(float|double), (\d+), (true|false), \d+, (\d+)", k) or
                  re.search(r"(fused_open_kernel)<(float|double), (\d+), \d+, (\d+)", k) or
-                 re.search(r"(chain_kernel)<(float|double), (\d+), \d+, (\d+), (\d+), (\d+), (\d+)", k))
+                 re.search(r"(chain_kernel)<(float|double), (\d+), \d+, (\d+), (\d+), (\d+), (\d+)", k) or
+                 re.search(r"(inc_erode_kernel)<(float|double), (\d+)>", k))
             if not m:
                 continue
             g = m.groups()
             if g[0] == "ring_kernel":
                 key = (int(g[2]), "ring %s" % ("dilate+flag" if g[3] == "true" else "erode"), "NP=%s" % g[4])
+            elif g[0] == "inc_erode_kernel":
+                key = (int(g[2]), "incremental erode", "")
             elif g[0] == "fused_open_kernel":
                 key = (int(g[2]), "fused open+flag", "NP=%s" % g[3])
             else:

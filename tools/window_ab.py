@@ -3,6 +3,7 @@
 in one process (developer tool; the per-radius switches in csrc/*.inc are written from its output).
 
     python tools/window_ab.py --libs neilpy_amd/_lib/variants/tw128.so --shapes 2048x16384,4096x4096 --windows 50 [--fused 0]
+    SMRF_ERO_INC=2 python tools/window_ab.py --libs parent.so --libs-env SMRF_ERO_INC=0 --windows 50
 
 Every build is called through ``smrf_progressive_filter_timed_f32|f64`` (an event per window boundary), ``--reps`` times
 after one warm-up, builds alternating; the table holds the median per window and the sum.  ``--fused 0|1|2`` sets
@@ -26,6 +27,8 @@ ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--dtype", default="f32", choices=["f32", "f64"])
 ap.add_argument("--fused", default=None)
 ap.add_argument("--json", default=None)
+ap.add_argument("--libs-env", default="", help="NAME=VALUE,... set for the --libs builds only (e.g. SMRF_ERO_INC=0: their ring "
+                "erosion beside this build's incremental one); the builds read their switches once, so each keeps its own")
 a = ap.parse_args()
 if a.fused is not None:
     os.environ["SMRF_FUSED"] = a.fused
@@ -36,11 +39,22 @@ from neilpy_amd import _lib  # noqa: E402
 lib = _lib.load()
 name_fn = "smrf_progressive_filter_timed_" + a.dtype
 fns = {"cur": getattr(lib, name_fn)}
+_lib.reload_switches()                                     # this build has read its environment before it changes
+side_env = dict(v.split("=", 1) for v in a.libs_env.split(",") if v)
+saved_env = {k: os.environ.get(k) for k in side_env}
+os.environ.update(side_env)
 for path in [v for v in a.libs.split(",") if v]:
     o = C.CDLL(os.path.abspath(path))
+    if side_env:
+        o.smrf_switches_reload()
     f = getattr(o, name_fn)
     f.restype, f.argtypes = fns["cur"].restype, fns["cur"].argtypes
     fns[os.path.basename(path).replace(".so", "")] = f
+for k, v in saved_env.items():
+    if v is None:
+        os.environ.pop(k)
+    else:
+        os.environ[k] = v
 npdt = np.float32 if a.dtype == "f32" else np.float64
 esz = 4 if a.dtype == "f32" else 8
 win = np.arange(a.first, a.windows + 1).astype(np.int32)
