@@ -35,6 +35,9 @@
  *   smrf_surface_*            slope(), aspect(), hillshade(), multiple_illumination(), esri_slope(), curvature(),
  *                             esri_curvature(), zevenbergen_and_thorne_curvature(), evans_curvature() and
  *                             wilson_gallant_curvature(), neilpy/neilpy.py:434-842 (host side: neilpy_amd/surface.py)
+ *   smrf_focal_*              std(), topographic_position_index() and reduce_peaks(), neilpy/neilpy.py:2039-2124,
+ *                             each scipy.ndimage.convolve(mode='nearest') plus cell-wise arithmetic (host side:
+ *                             neilpy_amd/focal.py)
  *
  * Conventions
  *   - every pointer named d_* is DEVICE memory (hipMalloc or a torch CUDA tensor's data_ptr);
@@ -445,6 +448,50 @@ SMRF_API int smrf_nearest_f64(const double* d_in, double* d_out, int64_t* d_src_
  * and d_col together, may be NULL. */
 SMRF_API int smrf_nearest_planes(const int64_t* d_src_index, const uint32_t* d_dist2, int64_t n, int cols,
                      double* d_dist, int64_t* d_row, int64_t* d_col, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * weighted focal sums: scipy.ndimage.convolve(mode='nearest') and what rests on it (neilpy_amd/focal.py; DESIGN.md
+ * section 12)
+ * ------------------------------------------------------------------------------------------ */
+#define SMRF_FOCAL_SUM 0      /* d_out0 T = conv(X) */
+#define SMRF_FOCAL_SUM_SQ 1   /* d_out0 T = conv(X), d_out1 T = conv(X*X), the square formed and rounded in T */
+#define SMRF_FOCAL_STD 2      /* std(), neilpy.py:2039 -> d_out0 float64, from the two sums and S = np.sum(strel) */
+#define SMRF_FOCAL_TPI 3      /* topographic_position_index(), :2098 -> d_out0 T = X - conv(X); the workspace's first
+                                 three doubles get sum(conv(X*X)), sum(X - conv(X)) and sd = sqrt(mean - mean**2),
+                                 the means and sd in T */
+#define SMRF_FOCAL_IMPL_AUTO 0    /* TILED when the whole halo fits SMRF_FOCAL_TILE_BYTES and the raster holds a tile */
+#define SMRF_FOCAL_IMPL_TILED 1   /* workgroup tile + halo of (kh / 2, kw / 2) cells in LDS; a larger kernel keeps the
+                                     largest common halo that fits and reads its other taps from global memory */
+#define SMRF_FOCAL_IMPL_DIRECT 2  /* every sample from global memory; same bits as TILED */
+#define SMRF_FOCAL_TILE_BYTES 53248 /* LDS of one tile: three workgroups per CU (160 KB) */
+
+/* 1 when the 64 x 8 tile plus the whole halo of a kh x kw kernel fits SMRF_FOCAL_TILE_BYTES (elem_size 4 or 8). */
+SMRF_API int smrf_focal_fits_tile(int kh, int kw, int elem_size);
+/* Workspace of a TPI launch and of smrf_focal_minmax_f64 over rows x cols cells. */
+SMRF_API size_t smrf_focal_workspace_bytes(int rows, int cols);
+/* One launch over a rows x cols raster (contiguous): d_X, or d_X - d_sub formed in T when d_sub is not NULL.  d_taps
+ * holds ntaps records (int32 drow, int32 dcol, float64 weight), the non-zero weights of a kh x kw kernel w in the order
+ * s = kh-1 .. 0, t = kw-1 .. 0 with drow = kh/2 - s, dcol = kw/2 - t.  conv = T(sum over the taps, in that order, of
+ * fp64(X[clamp(r + drow), clamp(c + dcol)]) * weight), each tap one fp64 multiply and one fp64 add.  The TPI sums are
+ * taken in a fixed order (no atomics): the same bits on every run. */
+SMRF_API int smrf_focal_f32(const float* d_X, const float* d_sub, int rows, int cols, int mode, const void* d_taps,
+                   int ntaps, int kh, int kw, double S, void* d_out0, void* d_out1, void* d_workspace,
+                   size_t workspace_bytes, int impl, void* stream);
+SMRF_API int smrf_focal_f64(const double* d_X, const double* d_sub, int rows, int cols, int mode, const void* d_taps,
+                   int ntaps, int kh, int kw, double S, void* d_out0, void* d_out1, void* d_workspace,
+                   size_t workspace_bytes, int impl, void* stream);
+/* d_io[i] /= T(d_sd[0]) over n cells: TPI's standardisation by the sd a TPI launch left at workspace + 2 doubles. */
+SMRF_API int smrf_focal_divide_f32(float* d_io, int64_t n, const double* d_sd, void* stream);
+SMRF_API int smrf_focal_divide_f64(double* d_io, int64_t n, const double* d_sd, void* stream);
+/* np.nanmin / np.nanmax of n float64 cells into the workspace's first two doubles (NaN when every cell is NaN). */
+SMRF_API int smrf_focal_minmax_f64(const double* d_x, int64_t n, void* d_workspace, size_t workspace_bytes,
+                   void* stream);
+/* reduce_peaks()'s tail, neilpy.py:2082-2085: V = (1 - interp(STD, (lo, hi), (0, 1)))**blend_rate,
+ * d_out = (1 - V)*M + V*Z in float64; d_lohi = (lo, hi) as smrf_focal_minmax_f64 leaves them. */
+SMRF_API int smrf_focal_mix_f32(const float* d_Z, const float* d_M, const double* d_STD, const double* d_lohi,
+                   double blend_rate, double* d_out, int64_t n, void* stream);
+SMRF_API int smrf_focal_mix_f64(const double* d_Z, const double* d_M, const double* d_STD, const double* d_lohi,
+                   double blend_rate, double* d_out, int64_t n, void* stream);
 
 #ifdef __cplusplus
 }

@@ -21,6 +21,9 @@ TERRAIN_OPENNESS, TERRAIN_SKYVIEW, TERRAIN_COUNT, TERRAIN_TERNARY = 0, 1, 2, 3
 (SURFACE_SLOPE, SURFACE_ASPECT, SURFACE_HILLSHADE, SURFACE_HORN, SURFACE_LAPLACE, SURFACE_ESRI, SURFACE_ZT,
  SURFACE_EVANS, SURFACE_WG) = range(9)
 SURFACE_OPT_RADIANS, SURFACE_OPT_DEGREES = 1, 2
+# weighted focal sums (include/smrf_hip.h): modes of smrf_focal_*, impl= of neilpy_amd.focal
+FOCAL_SUM, FOCAL_SUM_SQ, FOCAL_STD, FOCAL_TPI = range(4)
+FOCAL_IMPL_AUTO, FOCAL_IMPL_TILED, FOCAL_IMPL_DIRECT = 0, 1, 2
 
 
 class SmrfHipError(RuntimeError):
@@ -93,6 +96,15 @@ SIGNATURES = {
     "smrf_nearest_f32": (_i, [_p, _p, _p, _p, _i, _i, _p, _sz, _p]),
     "smrf_nearest_f64": (_i, [_p, _p, _p, _p, _i, _i, _p, _sz, _p]),
     "smrf_nearest_planes": (_i, [_p, _p, _i64, _i, _p, _p, _p, _p]),
+    "smrf_focal_fits_tile": (_i, [_i, _i, _i]),
+    "smrf_focal_workspace_bytes": (_sz, [_i, _i]),
+    "smrf_focal_f32": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _i, _d, _p, _p, _p, _sz, _i, _p]),
+    "smrf_focal_f64": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _i, _d, _p, _p, _p, _sz, _i, _p]),
+    "smrf_focal_divide_f32": (_i, [_p, _i64, _p, _p]),
+    "smrf_focal_divide_f64": (_i, [_p, _i64, _p, _p]),
+    "smrf_focal_minmax_f64": (_i, [_p, _i64, _p, _sz, _p]),
+    "smrf_focal_mix_f32": (_i, [_p, _p, _p, _p, _d, _p, _i64, _p]),
+    "smrf_focal_mix_f64": (_i, [_p, _p, _p, _p, _d, _p, _i64, _p]),
 }
 
 _lib = None
