@@ -38,6 +38,9 @@
  *   smrf_focal_*              std(), topographic_position_index() and reduce_peaks(), neilpy/neilpy.py:2039-2124,
  *                             each scipy.ndimage.convolve(mode='nearest') plus cell-wise arithmetic (host side:
  *                             neilpy_amd/focal.py)
+ *   smrf_morphometry_*, smrf_vip_*, smrf_ashift_*
+ *                             scaled_morphometry(), vip_score() and ashift(), neilpy/neilpy.py:2472, :1832, :1290
+ *                             (host side: neilpy_amd/morphometry.py)
  *
  * Conventions
  *   - every pointer named d_* is DEVICE memory (hipMalloc or a torch CUDA tensor's data_ptr);
@@ -492,6 +495,34 @@ SMRF_API int smrf_focal_mix_f32(const float* d_Z, const float* d_M, const double
                    double blend_rate, double* d_out, int64_t n, void* stream);
 SMRF_API int smrf_focal_mix_f64(const double* d_Z, const double* d_M, const double* d_STD, const double* d_lohi,
                    double blend_rate, double* d_out, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * strided stencils: scaled_morphometry, vip_score, ashift (neilpy_amd/morphometry.py)
+ * ------------------------------------------------------------------------------------------ */
+/* One sampling rule, ashift's (neilpy.py:1290): the sample at offset (dr, dc), each in {-n, 0, +n}, of cell (r, c) of
+ * the contiguous rows x cols raster d_Z is Z[r + dr, c + dc] where that row and that column are on the raster, and
+ * Z[r, c] otherwise.  n >= 1; n >= rows or n >= cols makes every sample along that axis the cell. */
+/* scaled_morphometry(), neilpy.py:2472: Wood's quadratic through nine samples n cells apart.  d0..d3 = 6*L**2, 3*L**2,
+ * 4*L**2, 6*L with L = cellsize * lookup_pixels, formed by the host in Python floats and rounded to T in the kernel.
+ * Every non-NULL output is written from one read of d_Z in one launch; a NULL one is neither computed nor stored.  No
+ * NaN repair: 0 / 0 on flats is NaN in the five ratio outputs. */
+SMRF_API int smrf_morphometry_f32(const float* d_Z, int rows, int cols, int n, double d0, double d1, double d2,
+                     double d3, float* d_A, float* d_S, float* d_K, float* d_K_profile, float* d_K_cross,
+                     float* d_K_long, float* d_K_tan, float* d_K_plan, void* stream);
+SMRF_API int smrf_morphometry_f64(const double* d_Z, int rows, int cols, int n, double d0, double d1, double d2,
+                     double d3, double* d_A, double* d_S, double* d_K, double* d_K_profile, double* d_K_cross,
+                     double* d_K_long, double* d_K_tan, double* d_K_plan, void* stream);
+/* vip_score(), neilpy.py:1832: the mean over the four lines through a cell (n = 1) of triangle_height(), :1818.
+ * x_diag = sqrt(2) * cellsize, x_axis = 1 * cellsize, b2_* = (2 * x_*)**2 as the host's scalar power gives them.  The
+ * neighbour differences are formed in T; everything after them, and d_out, is float64. */
+SMRF_API int smrf_vip_f32(const float* d_Z, int rows, int cols, double x_diag, double x_axis, double b2_diag,
+                     double b2_axis, double* d_out, void* stream);
+SMRF_API int smrf_vip_f64(const double* d_Z, int rows, int cols, double x_diag, double x_axis, double b2_diag,
+                     double b2_axis, double* d_out, void* stream);
+/* ashift(): d_out (not d_Z) gets the sample of direction 0..7 = (r-n, c-n), (r-n, c), (r-n, c+n), (r, c+n),
+ * (r+n, c+n), (r+n, c), (r+n, c-n), (r, c-n); any other direction copies the raster. */
+SMRF_API int smrf_ashift_f32(const float* d_Z, int rows, int cols, int direction, int n, float* d_out, void* stream);
+SMRF_API int smrf_ashift_f64(const double* d_Z, int rows, int cols, int direction, int n, double* d_out, void* stream);
 
 #ifdef __cplusplus
 }

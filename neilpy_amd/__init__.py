@@ -8,7 +8,8 @@ analyse the resulting DTM with the same kernels-only rule, and so do its local s
 / ``hillshade`` / the curvatures (neilpy_amd/surface.py).  ``inpaint_nearest`` is the third hole filler, an exact nearest-cell
 infill, and ``nearest_source`` the distance / index planes behind it (neilpy_amd/nearest.py).  ``focal_convolve`` is
 ``scipy.ndimage.convolve(mode='nearest')`` bit for bit, and ``std`` / ``topographic_position_index`` / ``reduce_peaks``
-rest on it (neilpy_amd/focal.py).
+rest on it (neilpy_amd/focal.py).  ``scaled_morphometry`` / ``vip_score`` / ``ashift`` are the multi-scale tools, strided
+stencils under ashift's edge rule, with the host helper ``triangle_height`` (neilpy_amd/morphometry.py).
 """
 from ._lib import SmrfHipError, load as load_library, LIB_PATH          # noqa: F401
 from .affine import Affine, edges_from_IT, from_origin, write_worldfile                 # noqa: F401
@@ -17,6 +18,7 @@ from .api import (create_dem, dilation, disk, erosion, inpaint_nans_by_fda, inpa
                   opening, progressive_filter, pssm, smrf)
 from .focal import distance_kernel, focal_convolve, reduce_peaks, std, topographic_position_index   # noqa: F401
 from .las import read_las, read_las_xyz, write_las                         # noqa: F401
+from .morphometry import ashift, scaled_morphometry, triangle_height, vip_score   # noqa: F401
 from .nearest import inpaint_nearest, nearest_source                      # noqa: F401
 from .surface import (aspect, curvature, esri_curvature, esri_slope, evans_curvature, hillshade,   # noqa: F401
                       multiple_illumination, slope, wilson_gallant_curvature, z_factor,

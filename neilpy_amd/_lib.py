@@ -105,6 +105,12 @@ SIGNATURES = {
     "smrf_focal_minmax_f64": (_i, [_p, _i64, _p, _sz, _p]),
     "smrf_focal_mix_f32": (_i, [_p, _p, _p, _p, _d, _p, _i64, _p]),
     "smrf_focal_mix_f64": (_i, [_p, _p, _p, _p, _d, _p, _i64, _p]),
+    "smrf_morphometry_f32": (_i, [_p, _i, _i, _i, _d, _d, _d, _d, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "smrf_morphometry_f64": (_i, [_p, _i, _i, _i, _d, _d, _d, _d, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "smrf_vip_f32": (_i, [_p, _i, _i, _d, _d, _d, _d, _p, _p]),
+    "smrf_vip_f64": (_i, [_p, _i, _i, _d, _d, _d, _d, _p, _p]),
+    "smrf_ashift_f32": (_i, [_p, _i, _i, _i, _i, _p, _p]),
+    "smrf_ashift_f64": (_i, [_p, _i, _i, _i, _i, _p, _p]),
 }
 
 _lib = None
