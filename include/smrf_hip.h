@@ -524,6 +524,35 @@ SMRF_API int smrf_vip_f64(const double* d_Z, int rows, int cols, double x_diag, 
 SMRF_API int smrf_ashift_f32(const float* d_Z, int rows, int cols, int direction, int n, float* d_out, void* stream);
 SMRF_API int smrf_ashift_f64(const double* d_Z, int rows, int cols, int direction, int n, double* d_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * nearest point of a cloud: uniform cell grid + ring search (neilpy_amd/points.py)
+ * ------------------------------------------------------------------------------------------ */
+/* Clouds are contiguous float64 (n, dim) arrays, dim 2 or 3, 1 <= npoints <= 2^30.  One workspace of
+ * smrf_points_nn_workspace_bytes(npoints, dim) bytes (0 for arguments out of range) serves all four calls below; the
+ * build leaves the grid in it and the search reads it, bounds and sum use its first 40 KB as scratch. */
+SMRF_API size_t smrf_points_nn_workspace_bytes(int64_t npoints, int dim);
+/* One reduction over a cloud: h_box = (min0, max0, min1, max1), the box of axes 0 and 1 (a NaN is skipped, an
+ * infinity is not), h_nonfinite = the number of coordinates, over all axes, that are NaN or infinite.  Synchronises the stream. */
+SMRF_API int smrf_points_nn_bounds_f64(const double* d_points, int64_t npoints, int dim, double* h_box,
+                     int64_t* h_nonfinite, void* d_workspace, size_t workspace_bytes, void* stream);
+/* The grid build: square cells over h_box (as the call above gave it for these points, all finite) on axes 0 and 1,
+ * sized for about two points per cell, at most 3 * max(1, npoints / 2) + 4 cells; the points are counted per cell with
+ * atomics, the counts scanned, and rows and coordinates scattered into cell order. */
+SMRF_API int smrf_points_nn_build_f64(const double* d_points, int64_t npoints, int dim, const double* h_box,
+                     void* d_workspace, size_t workspace_bytes, void* stream);
+/* The search, one thread per query point, over the grid the build left in the workspace for (d_points, npoints, dim,
+ * h_box): d_dist[i] = sqrt(((q0-p0)*(q0-p0) + (q1-p1)*(q1-p1)) [+ (q2-p2)*(q2-p2)]) in float64, every operation
+ * rounded, to the nearest point; d_index[i] = its row, the lowest among the points at that distance.  Either output may
+ * be NULL.  Queries may lie anywhere; they must be finite.  d_points names the cloud the workspace was built from; the
+ * kernel reads the cell-ordered copy of its coordinates in the workspace. */
+SMRF_API int smrf_points_nn_search_f64(const double* d_query, int64_t nquery, const double* d_points, int64_t npoints,
+                     int dim, const double* h_box, double* d_dist, int64_t* d_index, const void* d_workspace,
+                     size_t workspace_bytes, void* stream);
+/* d_sum[0] = the sum of n float64 values in a fixed order that depends on n only (per-workgroup partials in a fixed
+ * tree, then one workgroup; no float atomics): the same bits on every run. */
+SMRF_API int smrf_points_nn_sum_f64(const double* d_x, int64_t n, double* d_sum, void* d_workspace,
+                     size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

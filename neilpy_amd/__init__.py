@@ -10,6 +10,8 @@ infill, and ``nearest_source`` the distance / index planes behind it (neilpy_amd
 ``scipy.ndimage.convolve(mode='nearest')`` bit for bit, and ``std`` / ``topographic_position_index`` / ``reduce_peaks``
 rest on it (neilpy_amd/focal.py).  ``scaled_morphometry`` / ``vip_score`` / ``ashift`` are the multi-scale tools, strided
 stencils under ashift's edge rule, with the host helper ``triangle_height`` (neilpy_amd/morphometry.py).
+``chamfer_distance`` compares two point clouds and ``nearest_points`` is the exact nearest-neighbour query under it, a
+counting sort into a cell grid and a ring search (neilpy_amd/points.py).
 """
 from ._lib import SmrfHipError, load as load_library, LIB_PATH          # noqa: F401
 from .affine import Affine, edges_from_IT, from_origin, write_worldfile                 # noqa: F401
@@ -20,6 +22,7 @@ from .focal import distance_kernel, focal_convolve, reduce_peaks, std, topograph
 from .las import read_las, read_las_xyz, write_las                         # noqa: F401
 from .morphometry import ashift, scaled_morphometry, triangle_height, vip_score   # noqa: F401
 from .nearest import inpaint_nearest, nearest_source                      # noqa: F401
+from .points import chamfer_distance, nearest_points                       # noqa: F401
 from .surface import (aspect, curvature, esri_curvature, esri_slope, evans_curvature, hillshade,   # noqa: F401
                       multiple_illumination, slope, wilson_gallant_curvature, z_factor,
                       zevenbergen_and_thorne_curvature)

@@ -111,6 +111,11 @@ SIGNATURES = {
     "smrf_vip_f64": (_i, [_p, _i, _i, _d, _d, _d, _d, _p, _p]),
     "smrf_ashift_f32": (_i, [_p, _i, _i, _i, _i, _p, _p]),
     "smrf_ashift_f64": (_i, [_p, _i, _i, _i, _i, _p, _p]),
+    "smrf_points_nn_workspace_bytes": (_sz, [_i64, _i]),
+    "smrf_points_nn_bounds_f64": (_i, [_p, _i64, _i, C.POINTER(_d), C.POINTER(_i64), _p, _sz, _p]),
+    "smrf_points_nn_build_f64": (_i, [_p, _i64, _i, C.POINTER(_d), _p, _sz, _p]),
+    "smrf_points_nn_search_f64": (_i, [_p, _i64, _p, _i64, _i, C.POINTER(_d), _p, _p, _p, _sz, _p]),
+    "smrf_points_nn_sum_f64": (_i, [_p, _i64, _p, _p, _sz, _p]),
 }
 
 _lib = None
