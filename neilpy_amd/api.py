@@ -16,7 +16,8 @@ import numpy as np
 
 from . import _lib
 from ._device import device_scoped as _device_scoped, is_tensor as _is_tensor
-from ._xfer import to_device as _h2d, to_host as _d2h
+from ._raster import Raster, _ptr, _stream, _suffix, _to_device, _torch
+from ._xfer import to_host as _d2h
 from .affine import from_origin
 
 __all__ = ["disk", "erosion", "dilation", "opening", "progressive_filter", "create_dem",
@@ -24,43 +25,6 @@ __all__ = ["disk", "erosion", "dilation", "opening", "progressive_filter", "crea
 
 #: statistics of the most recent calls (LSQR istop / itn, unknown counts), SURVEY section 5
 last_stats = {}
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def _stream():
-    return C.c_void_p(_torch().cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _to_device(a, dtype=None):
-    """NumPy / tensor -> contiguous CUDA tensor (float32 and float64 kept, others -> float64)."""
-    torch = _torch()
-    _lib.require_gpu()
-    if _is_tensor(a):
-        t = a
-    else:
-        arr = np.asarray(a)
-        if dtype is None and arr.dtype not in (np.float32, np.float64):
-            arr = arr.astype(np.float64)
-        t = _h2d(arr)                                      # pinned staging for large arrays
-    if dtype is not None and t.dtype != dtype:
-        t = t.to(dtype)
-    if t.dtype not in (torch.float32, torch.float64):
-        t = t.to(torch.float64)
-    if not t.is_cuda:
-        t = t.cuda()
-    return t.contiguous()
-
-
-def _suffix(t):
-    return "f32" if t.dtype == _torch().float32 else "f64"
 
 
 # ------------------------------------------------------------------------------------------
@@ -92,48 +56,35 @@ def _has_nan(t):
     return cnt.value > 0
 
 
-def _disk_filter(image, radius, dilate, impl, nan_aware=None):
-    torch = _torch()
-    was_tensor = _is_tensor(image)
-    src = _to_device(image)
-    if src.dim() != 2:
-        raise ValueError("expected a 2-D raster")
-    rows, cols = src.shape
-    if rows == 0 or cols == 0:
-        out = src.clone()
-        return out if was_tensor else _d2h(out)
-    if nan_aware is None:
-        nan_aware = _has_nan(src)
-    out = torch.empty_like(src)
-    lib = _lib.load()
-    fn = getattr(lib, "smrf_disk_filter_" + _suffix(src))
-    _lib.check(fn(_ptr(src), _ptr(out), rows, cols, cols, 0, rows, 0, rows, int(radius), int(bool(dilate)),
-                  int(bool(nan_aware)), int(impl), _stream()))
-    return out if was_tensor else _d2h(out)
+def _disk_filter(image, radius, passes, impl):
+    """the disk erosions (False) and dilations (True) of ``passes``, one after the other, with one NaN count"""
+    R = Raster(image)
+    nan_aware = _has_nan(R.t) if R.t.numel() else False
+    src = R.t
+    for dilate in passes:
+        out = R.empty()
+        R.call("disk_filter", _ptr(src), _ptr(out), R.rows, R.cols, R.cols, 0, R.rows, 0, R.rows, int(radius),
+               int(bool(dilate)), int(bool(nan_aware)), int(impl))
+        src = out
+    return R.out(src)
 
 
 @_device_scoped
 def erosion(image, footprint=None, *, radius=None, impl=_lib.IMPL_AUTO):
     """Grey erosion by ``disk(r)``, borders ``mode='reflect'`` (scipy.ndimage.grey_erosion)."""
-    return _disk_filter(image, _radius_of(footprint, radius), False, impl)
+    return _disk_filter(image, _radius_of(footprint, radius), (False,), impl)
 
 
 @_device_scoped
 def dilation(image, footprint=None, *, radius=None, impl=_lib.IMPL_AUTO):
     """Grey dilation by ``disk(r)``, borders ``mode='reflect'`` (scipy.ndimage.grey_dilation)."""
-    return _disk_filter(image, _radius_of(footprint, radius), True, impl)
+    return _disk_filter(image, _radius_of(footprint, radius), (True,), impl)
 
 
 @_device_scoped
 def opening(image, footprint=None, *, radius=None, impl=_lib.IMPL_AUTO):
     """skimage.morphology.opening(image, disk(r)) = dilation(erosion(image))."""
-    r = _radius_of(footprint, radius)
-    was_tensor = _is_tensor(image)
-    src = _to_device(image)
-    nan_aware = _has_nan(src) if src.numel() else False
-    e = _disk_filter(src, r, False, impl, nan_aware)
-    o = _disk_filter(e, r, True, impl, nan_aware)
-    return o if was_tensor else _d2h(o)
+    return _disk_filter(image, _radius_of(footprint, radius), (False, True), impl)
 
 
 # ------------------------------------------------------------------------------------------
@@ -510,11 +461,8 @@ def pssm(Z, cellsize=1, ve=2.3, reverse=False, apply_colormap=True):
     reference keeps float32 rasters in float32, which can move a class by one at a rounding tie).
     """
     torch = _torch()
-    was_tensor = _is_tensor(Z)
-    Zd = _to_device(Z, torch.float64)
-    if Zd.dim() != 2:
-        raise ValueError("expected a 2-D raster")
-    rows, cols = Zd.shape
+    R = Raster(Z, torch.float64)
+    Zd, rows, cols = R.t, R.rows, R.cols
     if rows < 2 or cols < 2:
         raise ValueError("Shape of array too small to calculate a numerical gradient, "
                          "at least (edge_order + 1) elements are required.")      # np.gradient's message
@@ -531,5 +479,4 @@ def pssm(Z, cellsize=1, ve=2.3, reverse=False, apply_colormap=True):
         P = torch.empty((rows, cols), dtype=torch.uint8, device=Zd.device)
     _lib.check(lib.smrf_pssm_f64(_ptr(Zd), _ptr(P), _ptr(rgba), _ptr(lut), rows, cols, float(cellsize), float(ve),
                                  _stream()))
-    out = rgba if apply_colormap else P
-    return out if was_tensor else _d2h(out)
+    return R.out(rgba if apply_colormap else P)

@@ -16,7 +16,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "smrf_common.h"
+#include "raster_stencil.h"
 
 namespace {
 
@@ -249,8 +249,8 @@ inline long long n_workgroups(int rows, int cols) {
 }
 
 template <typename T, int MODE>
-hipError_t launch_mode(const FocalArgs<T>& a, bool tiled, hipStream_t st) {
-  const dim3 grid((a.cols + TX - 1) / TX, (a.rows + TY - 1) / TY), block(TX, TY);
+hipError_t launch_mode(const FocalArgs<T>& a, bool tiled, unsigned gy, hipStream_t st) {
+  const dim3 grid((a.cols + TX - 1) / TX, gy), block(TX, TY);
   if (tiled)
     hipLaunchKernelGGL((focal_kernel<T, MODE, true>), grid, block, tile_bytes(a.hr, a.hc, sizeof(T)), st, a);
   else
@@ -261,14 +261,15 @@ hipError_t launch_mode(const FocalArgs<T>& a, bool tiled, hipStream_t st) {
 template <typename T>
 int focal(const T* d_X, const T* d_sub, int rows, int cols, int mode, const void* d_taps, int ntaps, int kh, int kw,
           double S, void* d_out0, void* d_out1, void* d_ws, size_t ws_bytes, int impl, void* stream) {
-  if (rows < 0 || cols < 0 || ntaps < 0) return smrf_fail(SMRF_E_ARG, "negative size");
+  if (int rc = smrf::check_size(rows, cols, ntaps)) return rc;
   if (kh < 1 || kw < 1) return smrf_fail(SMRF_E_ARG, "kernel of %d x %d", kh, kw);
   if (mode < SMRF_FOCAL_SUM || mode > SMRF_FOCAL_TPI) return smrf_fail(SMRF_E_ARG, "unknown mode %d", mode);
   if (impl < SMRF_FOCAL_IMPL_AUTO || impl > SMRF_FOCAL_IMPL_DIRECT) return smrf_fail(SMRF_E_ARG, "unknown impl %d", impl);
-  if ((long long)rows * cols == 0) return SMRF_OK;
+  if (smrf::empty_raster(rows, cols)) return SMRF_OK;
   if (!d_X || !d_out0 || (ntaps > 0 && !d_taps)) return smrf_fail(SMRF_E_ARG, "null pointer");
   if (mode == SMRF_FOCAL_SUM_SQ && !d_out1) return smrf_fail(SMRF_E_ARG, "null output");
-  if ((rows + TY - 1) / TY > 65535) return smrf_fail(SMRF_E_ARG, "%d rows exceed the launch grid", rows);
+  unsigned gy = 0;
+  if (int rc = smrf::grid_rows(rows, TY, gy)) return rc;
   const long long nwg = n_workgroups(rows, cols);
   if (mode == SMRF_FOCAL_TPI && (!d_ws || ws_bytes < smrf_focal_workspace_bytes(rows, cols)))
     return smrf_fail(SMRF_E_WORKSPACE, "workspace of %zu bytes, %zu needed", ws_bytes,
@@ -288,10 +289,10 @@ int focal(const T* d_X, const T* d_sub, int rows, int cols, int mode, const void
   const hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipSuccess;
   switch (mode) {
-    case SMRF_FOCAL_SUM: e = launch_mode<T, SMRF_FOCAL_SUM>(a, tiled, st); break;
-    case SMRF_FOCAL_SUM_SQ: e = launch_mode<T, SMRF_FOCAL_SUM_SQ>(a, tiled, st); break;
-    case SMRF_FOCAL_STD: e = launch_mode<T, SMRF_FOCAL_STD>(a, tiled, st); break;
-    default: e = launch_mode<T, SMRF_FOCAL_TPI>(a, tiled, st); break;
+    case SMRF_FOCAL_SUM: e = launch_mode<T, SMRF_FOCAL_SUM>(a, tiled, gy, st); break;
+    case SMRF_FOCAL_SUM_SQ: e = launch_mode<T, SMRF_FOCAL_SUM_SQ>(a, tiled, gy, st); break;
+    case SMRF_FOCAL_STD: e = launch_mode<T, SMRF_FOCAL_STD>(a, tiled, gy, st); break;
+    default: e = launch_mode<T, SMRF_FOCAL_TPI>(a, tiled, gy, st); break;
   }
   SMRF_HIP_CHECK(e);
   if (mode == SMRF_FOCAL_TPI) {

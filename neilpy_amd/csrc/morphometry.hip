@@ -14,31 +14,12 @@
 // Arithmetic follows DESIGN.md section 13 (tests/morphometry_numpy.py) operation by operation in the reference's order.
 // The library builds with -ffp-contract=off and fp32 divide and sqrt stay correctly rounded, so every output that needs
 // no transcendental function gives the reference's bits.
-#include <cmath>
-
-#include "smrf_common.h"
+#include "raster_stencil.h"
 
 namespace smrf {
 
 constexpr int MX = 64, MY = 4;   // 64 columns x 4 strips per workgroup
 constexpr int MR = 4;            // rows per strip
-
-template <typename T>
-struct MorphConsts;
-template <>
-struct MorphConsts<float> {
-  static constexpr float rad2deg = 180.0f / 3.14159265358979323846f;   // np.rad2deg on float32: 180f / float(pi)
-};
-template <>
-struct MorphConsts<double> {
-  static constexpr double rad2deg = 180.0 / 3.14159265358979323846;
-};
-
-// the nine samples of one cell at stride n, z1..z9 in reading order (z5 = X)
-template <typename T>
-struct Ring {
-  T z1, z2, z3, z4, X, z6, z7, z8, z9;
-};
 
 // Column offsets and their validity are the thread's; row offsets the step's.  p = &Z[r, 0].
 template <typename T>
@@ -85,25 +66,24 @@ struct MorphArgs {
 
 template <typename T>
 __device__ inline void morph_cell(const MorphArgs<T>& a, const Ring<T>& g, long long idx) {
+  // the quadratic shared with evans_curvature (raster_stencil.h); the divisors are converted once, up front
   const T L2x6 = (T)a.d0, L2x3 = (T)a.d1, L2x4 = (T)a.d2, Lx6 = (T)a.d3;
-  const T X = g.X;
-  const T A = (g.z1 + g.z3 + g.z4 + g.z6 + g.z7 + g.z9) / L2x6 - (g.z2 + X + g.z8) / L2x3;
-  const T B = (g.z1 + g.z2 + g.z3 + g.z7 + g.z8 + g.z9) / L2x6 - (g.z4 + X + g.z6) / L2x3;
-  if (a.out[2]) a.out[2][idx] = T(-2) * (A + B);
+  Evans<T> q;
+  q.set_AB(g, L2x6, L2x3);
+  if (a.out[2]) a.out[2][idx] = q.K();
   if (!(a.out[0] || a.out[1] || a.out[3] || a.out[4] || a.out[5] || a.out[6] || a.out[7])) return;
-  const T D = (g.z3 + g.z6 + g.z9 - g.z1 - g.z4 - g.z7) / Lx6;
-  const T E = (g.z1 + g.z2 + g.z3 - g.z7 - g.z8 - g.z9) / Lx6;
-  if (a.out[0]) a.out[0][idx] = mod360(T(270) - atan2(E, D) * MorphConsts<T>::rad2deg);
-  const T DD = D * D, EE = E * E, S2 = DD + EE;
-  if (a.out[1]) a.out[1][idx] = atan(sqrt(S2)) * MorphConsts<T>::rad2deg;
+  q.set_DE(g, Lx6);
+  if (a.out[0]) a.out[0][idx] = mod360(T(270) - atan2(q.E, q.D) * Consts<T>::rad2deg);
+  q.set_S2();
+  if (a.out[1]) a.out[1][idx] = atan(sqrt(q.S2)) * Consts<T>::rad2deg;
   if (!(a.out[3] || a.out[4] || a.out[5] || a.out[6] || a.out[7])) return;
-  const T C = (g.z3 + g.z7 - g.z1 - g.z9) / L2x4;
+  q.set_C(g, L2x4);
   // no NaN repair: 0 / 0 on flats propagates
-  if (a.out[3]) a.out[3][idx] = -(A * DD + T(2) * C * D * E + B * EE) / (S2 * (T)pow(S2 + T(1), T(1.5)));
-  if (a.out[4]) a.out[4][idx] = T(-2) * (B * DD + A * EE - C * D * E) / S2;
-  if (a.out[5]) a.out[5][idx] = T(-2) * (A * DD + B * EE + C * D * E) / S2;
-  if (a.out[6]) a.out[6][idx] = -(A * EE - T(2) * C * D * E + B * DD) / (S2 * sqrt(S2 + T(1)));
-  if (a.out[7]) a.out[7][idx] = -(A * EE - T(2) * C * D * E + B * DD) / (T)pow(S2, T(1.5));
+  if (a.out[3]) a.out[3][idx] = q.K_profile();
+  if (a.out[4]) a.out[4][idx] = q.K_cross();
+  if (a.out[5]) a.out[5][idx] = q.K_long();
+  if (a.out[6]) a.out[6][idx] = q.K_tan();
+  if (a.out[7]) a.out[7][idx] = q.K_plan();
 }
 
 template <typename T>
@@ -186,17 +166,16 @@ __global__ __launch_bounds__(MX* MY) void ashift_kernel(ShiftArgs<T> a) {
 }
 
 static int grid_of(int rows, int cols, dim3& grid) {
-  const long long gy = ((long long)rows + MY * MR - 1) / (MY * MR);
-  if (gy > 65535) return smrf_fail(SMRF_E_ARG, "%d rows exceed the launch grid", rows);
-  grid = dim3((cols + MX - 1) / MX, (unsigned)gy);
+  unsigned gy = 0;
+  if (int rc = grid_rows(rows, MY * MR, gy)) return rc;
+  grid = dim3((cols + MX - 1) / MX, gy);
   return SMRF_OK;
 }
 
 static int check_raster(const void* d_Z, int rows, int cols, bool& empty) {
-  if (rows < 0 || cols < 0) return smrf_fail(SMRF_E_ARG, "negative size");
-  empty = (long long)rows * cols == 0;
-  if (!empty && !d_Z) return smrf_fail(SMRF_E_ARG, "null raster");
-  return SMRF_OK;
+  if (int rc = check_size(rows, cols)) return rc;
+  empty = empty_raster(rows, cols);
+  return empty ? SMRF_OK : check_raster_ptr(d_Z);
 }
 
 template <typename T>
@@ -239,10 +218,9 @@ int ashift(const T* d_Z, int rows, int cols, int direction, int n, T* d_out, voi
   if (empty) return SMRF_OK;
   if (!d_out) return smrf_fail(SMRF_E_ARG, "null output");
   if (d_out == d_Z) return smrf_fail(SMRF_E_ARG, "ashift cannot run in place");
-  // clockwise from the upper left; any other direction leaves the raster as it is
-  static const int DR[8] = {-1, -1, -1, 0, 1, 1, 1, 0}, DC[8] = {-1, 0, 1, 1, 1, 0, -1, -1};
+  // any direction but the eight of the table leaves the raster as it is
   const bool known = direction >= 0 && direction < 8;
-  ShiftArgs<T> a{d_Z, rows, cols, known ? (long long)DR[direction] * n : 0, known ? (long long)DC[direction] * n : 0, d_out};
+  ShiftArgs<T> a{d_Z, rows, cols, known ? (long long)kDR[direction] * n : 0, known ? (long long)kDC[direction] * n : 0, d_out};
   dim3 grid;
   if (int rc = grid_of(rows, cols, grid)) return rc;
   hipLaunchKernelGGL(ashift_kernel<T>, grid, dim3(MX, MY), 0, (hipStream_t)stream, a);

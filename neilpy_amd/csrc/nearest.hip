@@ -18,7 +18,7 @@
 // Sources are never written, so in == out is safe: a hole only reads source cells.
 #include <climits>
 
-#include "smrf_common.h"
+#include "raster_stencil.h"
 
 namespace smrf {
 
@@ -278,11 +278,11 @@ __global__ __launch_bounds__(256) void nearest_planes_kernel(const long long* in
 template <typename T>
 int nearest(const T* d_in, T* d_out, int64_t* d_index, uint32_t* d_dist2, int rows, int cols, void* d_ws, size_t ws_bytes,
             void* stream) {
-  if (rows < 0 || cols < 0) return smrf_fail(SMRF_E_ARG, "negative size");
-  if ((long long)rows * cols == 0) return SMRF_OK;
+  if (int rc = check_size(rows, cols)) return rc;
+  if (empty_raster(rows, cols)) return SMRF_OK;
   if (rows > NMAX || cols > NMAX)
     return smrf_fail(SMRF_E_ARG, "%d x %d: squared distances beyond %d cells per axis do not fit 32 bits", rows, cols, NMAX);
-  if (!d_in) return smrf_fail(SMRF_E_ARG, "null raster");
+  if (int rc = check_raster_ptr(d_in)) return rc;
   if (!d_out && !d_index && !d_dist2) return smrf_fail(SMRF_E_ARG, "null output");
   if (!d_ws || ws_bytes < nearest_layout(rows, cols, nullptr, nullptr))
     return smrf_fail(SMRF_E_WORKSPACE, "workspace of %zu bytes, %zu needed", ws_bytes,

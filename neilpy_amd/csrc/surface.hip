@@ -15,7 +15,7 @@
 // needs no transcendental function gives the reference's bits.
 #include <cmath>
 
-#include "smrf_common.h"
+#include "raster_stencil.h"
 
 namespace smrf {
 
@@ -31,21 +31,6 @@ struct SurfArgs {
   const double* ang;   // [n_ang][3]: cos zenith, sin zenith, azimuth (radians)
   int n_ang;
   void* out[6];
-};
-
-template <typename T>
-struct Consts;
-template <>
-struct Consts<float> {
-  static constexpr float rad2deg = 180.0f / 3.14159265358979323846f;   // np.rad2deg on float32: 180f / float(pi)
-  static constexpr float half_pi = (float)(3.14159265358979323846 / 2);
-  static constexpr float two_pi = (float)(2 * 3.14159265358979323846);
-};
-template <>
-struct Consts<double> {
-  static constexpr double rad2deg = 180.0 / 3.14159265358979323846;
-  static constexpr double half_pi = 3.14159265358979323846 / 2;
-  static constexpr double two_pi = 2 * 3.14159265358979323846;
 };
 
 template <typename T>
@@ -144,34 +129,33 @@ __device__ inline void cell(const SurfArgs<T>& a, const Win<T>& w, long long idx
     const T lap = (T)(c * -2.0 + (u + d)) + (T)(c * -2.0 + (l + r));
     put<T>(a.out[0], idx, T(-100) * lap);
   } else {
-    // ashift ring, z1..z9 in reading order (z5 = X)
-    T z1 = ash(w, 0, 0, top, bot, lft, rgt), z2 = ash(w, 0, 1, top, bot, lft, rgt),
-      z3 = ash(w, 0, 2, top, bot, lft, rgt), z4 = ash(w, 1, 0, top, bot, lft, rgt),
-      z6 = ash(w, 1, 2, top, bot, lft, rgt), z7 = ash(w, 2, 0, top, bot, lft, rgt),
-      z8 = ash(w, 2, 1, top, bot, lft, rgt), z9 = ash(w, 2, 2, top, bot, lft, rgt);
+    // ashift's ring from the window
+    Ring<T> g{ash(w, 0, 0, top, bot, lft, rgt), ash(w, 0, 1, top, bot, lft, rgt), ash(w, 0, 2, top, bot, lft, rgt),
+              ash(w, 1, 0, top, bot, lft, rgt), X, ash(w, 1, 2, top, bot, lft, rgt),
+              ash(w, 2, 0, top, bot, lft, rgt), ash(w, 2, 1, top, bot, lft, rgt), ash(w, 2, 2, top, bot, lft, rgt)};
     const T X2 = T(2) * X;
     if constexpr (MODE == SMRF_SURFACE_ESRI) {
       // a NaN neighbour is the cell itself
-      z1 = z1 != z1 ? X : z1; z2 = z2 != z2 ? X : z2; z3 = z3 != z3 ? X : z3; z4 = z4 != z4 ? X : z4;
-      z6 = z6 != z6 ? X : z6; z7 = z7 != z7 ? X : z7; z8 = z8 != z8 ? X : z8; z9 = z9 != z9 ? X : z9;
+      auto self = [X](T& z) { z = z != z ? X : z; };
+      self(g.z1); self(g.z2); self(g.z3); self(g.z4); self(g.z6); self(g.z7); self(g.z8); self(g.z9);
     } else if constexpr (MODE == SMRF_SURFACE_ZT || MODE == SMRF_SURFACE_EVANS) {
       // a NaN neighbour is 2X - the opposite one, filled in this order (later fills see earlier ones)
-      if (z1 != z1) z1 = X2 - z9;
-      if (z2 != z2) z2 = X2 - z8;
-      if (z3 != z3) z3 = X2 - z7;
-      if (z4 != z4) z4 = X2 - z6;
-      if (z6 != z6) z6 = X2 - z4;
-      if (z7 != z7) z7 = X2 - z3;
-      if (z8 != z8) z8 = X2 - z2;
-      if (z9 != z9) z9 = X2 - z1;
+      if (g.z1 != g.z1) g.z1 = X2 - g.z9;
+      if (g.z2 != g.z2) g.z2 = X2 - g.z8;
+      if (g.z3 != g.z3) g.z3 = X2 - g.z7;
+      if (g.z4 != g.z4) g.z4 = X2 - g.z6;
+      if (g.z6 != g.z6) g.z6 = X2 - g.z4;
+      if (g.z7 != g.z7) g.z7 = X2 - g.z3;
+      if (g.z8 != g.z8) g.z8 = X2 - g.z2;
+      if (g.z9 != g.z9) g.z9 = X2 - g.z1;
     }
     if constexpr (MODE == SMRF_SURFACE_ESRI || MODE == SMRF_SURFACE_ZT) {
       const T L2 = (T)a.p0, L2x4 = (T)a.p1, Lx2 = (T)a.p2;
-      const T D = (((z4 + z6) / T(2)) - X) / L2;
-      const T E = (((z2 + z8) / T(2)) - X) / L2;
-      const T F = (-z1 + z3 + z7 - z9) / L2x4;
-      const T G = (-z4 + z6) / Lx2;
-      const T H = (z2 - z8) / Lx2;
+      const T D = (((g.z4 + g.z6) / T(2)) - X) / L2;
+      const T E = (((g.z2 + g.z8) / T(2)) - X) / L2;
+      const T F = (-g.z1 + g.z3 + g.z7 - g.z9) / L2x4;
+      const T G = (-g.z4 + g.z6) / Lx2;
+      const T H = (g.z2 - g.z8) / Lx2;
       const T GG = G * G, HH = H * H;
       if constexpr (MODE == SMRF_SURFACE_ESRI) {
         put<T>(a.out[0], idx, T(-200) * (D + E));
@@ -188,26 +172,26 @@ __device__ inline void cell(const SurfArgs<T>& a, const Win<T>& w, long long idx
         if (a.out[5]) put<T>(a.out[5], idx, zero_nan(T(2) * (D * HH + E * GG - F * G * H) / P));
       }
     } else if constexpr (MODE == SMRF_SURFACE_EVANS) {
+      // the quadratic shared with scaled_morphometry (raster_stencil.h), here on the NaN-filled ring
       const T L2x6 = (T)a.p0, L2x3 = (T)a.p1, L2x4 = (T)a.p2, Lx6 = (T)a.p3;
-      const T A = (z1 + z3 + z4 + z6 + z7 + z9) / L2x6 - (z2 + X + z8) / L2x3;
-      const T B = (z1 + z2 + z3 + z7 + z8 + z9) / L2x6 - (z4 + X + z6) / L2x3;
-      const T C = (z3 + z7 - z1 - z9) / L2x4;
-      const T D = (z3 + z6 + z9 - z1 - z4 - z7) / Lx6;
-      const T E = (z1 + z2 + z3 - z7 - z8 - z9) / Lx6;
-      const T DD = D * D, EE = E * E, S2 = DD + EE;
+      Evans<T> q;
+      q.set_AB(g, L2x6, L2x3);
+      q.set_C(g, L2x4);
+      q.set_DE(g, Lx6);
+      q.set_S2();
       // Evans sets NaN to 0 in its five ratios where X is finite
       const bool fin = X - X == T(0);
       auto fix = [fin](T v) { return (v != v && fin) ? T(0) : v; };
-      put<T>(a.out[0], idx, T(-2) * (A + B));
-      if (a.out[1]) put<T>(a.out[1], idx, fix(-(A * DD + T(2) * C * D * E + B * EE) / (S2 * (T)pow(S2 + T(1), T(1.5)))));
-      if (a.out[2]) put<T>(a.out[2], idx, fix(-(A * EE - T(2) * C * D * E + B * DD) / (T)pow(S2, T(1.5))));
-      if (a.out[3]) put<T>(a.out[3], idx, fix(-(A * EE - T(2) * C * D * E + B * DD) / (S2 * sqrt(S2 + T(1)))));
-      if (a.out[4]) put<T>(a.out[4], idx, fix(T(-2) * (A * DD + B * EE + C * D * E) / S2));
-      if (a.out[5]) put<T>(a.out[5], idx, fix(T(-2) * (B * DD + A * EE - C * D * E) / S2));
+      put<T>(a.out[0], idx, q.K());
+      if (a.out[1]) put<T>(a.out[1], idx, fix(q.K_profile()));
+      if (a.out[2]) put<T>(a.out[2], idx, fix(q.K_plan()));
+      if (a.out[3]) put<T>(a.out[3], idx, fix(q.K_tan()));
+      if (a.out[4]) put<T>(a.out[4], idx, fix(q.K_long()));
+      if (a.out[5]) put<T>(a.out[5], idx, fix(q.K_cross()));
     } else {
       // Wilson-Gallant numbering: Z1 upper right, clockwise to Z6 left; Z7 = Z8 = X (the reference's ashift(X, 8)
       // and ashift(X, 9) do not move), Z9 = X
-      T w1 = z3, w2 = z6, w3 = z9, w4 = z8, w5 = z7, w6 = z4, w7 = X, w8 = X;
+      T w1 = g.z3, w2 = g.z6, w3 = g.z9, w4 = g.z8, w5 = g.z7, w6 = g.z4, w7 = X, w8 = X;
       if (w1 != w1) w1 = X2 - w5;
       if (w2 != w2) w2 = X2 - w6;
       if (w3 != w3) w3 = X2 - w7;
@@ -264,9 +248,8 @@ __global__ __launch_bounds__(SX* SY) void surface_kernel(SurfArgs<T> a) {
 }
 
 template <typename T, int MODE>
-hipError_t launch_surface(const SurfArgs<T>& a, hipStream_t st) {
-  const int strips = (a.rows + SR - 1) / SR;
-  const dim3 grid((a.cols + SX - 1) / SX, (strips + SY - 1) / SY), block(SX, SY);
+hipError_t launch_surface(const SurfArgs<T>& a, unsigned gy, hipStream_t st) {
+  const dim3 grid((a.cols + SX - 1) / SX, gy), block(SX, SY);
   hipLaunchKernelGGL((surface_kernel<T, MODE>), grid, block, 0, st, a);
   return hipGetLastError();
 }
@@ -275,10 +258,10 @@ template <typename T>
 int surface(const T* d_Z, int rows, int cols, int mode, int options, double p0, double p1, double p2, double p3,
             const double* d_angles, int n_angles, void* d_out0, void* d_out1, void* d_out2, void* d_out3,
             void* d_out4, void* d_out5, void* stream) {
-  if (rows < 0 || cols < 0) return smrf_fail(SMRF_E_ARG, "negative size");
+  if (int rc = check_size(rows, cols)) return rc;
   if (mode < SMRF_SURFACE_SLOPE || mode > SMRF_SURFACE_WG) return smrf_fail(SMRF_E_ARG, "unknown mode %d", mode);
-  if ((long long)rows * cols == 0) return SMRF_OK;
-  if (!d_Z) return smrf_fail(SMRF_E_ARG, "null raster");
+  if (empty_raster(rows, cols)) return SMRF_OK;
+  if (int rc = check_raster_ptr(d_Z)) return rc;
   const bool gradient = mode == SMRF_SURFACE_SLOPE || mode == SMRF_SURFACE_ASPECT || mode == SMRF_SURFACE_HILLSHADE;
   if (gradient && (rows < 2 || cols < 2))
     return smrf_fail(SMRF_E_ARG, "np.gradient needs at least 2 cells per axis (%d x %d)", rows, cols);
@@ -293,22 +276,22 @@ int surface(const T* d_Z, int rows, int cols, int mode, int options, double p0, 
   } else if (!d_out0) {
     return smrf_fail(SMRF_E_ARG, "null output");
   }
-  const long long strips = (rows + SR - 1) / SR;
-  if ((strips + SY - 1) / SY > 65535) return smrf_fail(SMRF_E_ARG, "%d rows exceed the launch grid", rows);
+  unsigned gy = 0;
+  if (int rc = grid_rows(rows, SY * SR, gy)) return rc;
   SurfArgs<T> a{d_Z, rows, cols, options, p0, p1, p2, p3, d_angles, n_angles, {}};
   for (int k = 0; k < 6; ++k) a.out[k] = outs[k];
   const hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipSuccess;
   switch (mode) {
-    case SMRF_SURFACE_SLOPE: e = launch_surface<T, SMRF_SURFACE_SLOPE>(a, st); break;
-    case SMRF_SURFACE_ASPECT: e = launch_surface<T, SMRF_SURFACE_ASPECT>(a, st); break;
-    case SMRF_SURFACE_HILLSHADE: e = launch_surface<T, SMRF_SURFACE_HILLSHADE>(a, st); break;
-    case SMRF_SURFACE_HORN: e = launch_surface<T, SMRF_SURFACE_HORN>(a, st); break;
-    case SMRF_SURFACE_LAPLACE: e = launch_surface<T, SMRF_SURFACE_LAPLACE>(a, st); break;
-    case SMRF_SURFACE_ESRI: e = launch_surface<T, SMRF_SURFACE_ESRI>(a, st); break;
-    case SMRF_SURFACE_ZT: e = launch_surface<T, SMRF_SURFACE_ZT>(a, st); break;
-    case SMRF_SURFACE_EVANS: e = launch_surface<T, SMRF_SURFACE_EVANS>(a, st); break;
-    default: e = launch_surface<T, SMRF_SURFACE_WG>(a, st); break;
+    case SMRF_SURFACE_SLOPE: e = launch_surface<T, SMRF_SURFACE_SLOPE>(a, gy, st); break;
+    case SMRF_SURFACE_ASPECT: e = launch_surface<T, SMRF_SURFACE_ASPECT>(a, gy, st); break;
+    case SMRF_SURFACE_HILLSHADE: e = launch_surface<T, SMRF_SURFACE_HILLSHADE>(a, gy, st); break;
+    case SMRF_SURFACE_HORN: e = launch_surface<T, SMRF_SURFACE_HORN>(a, gy, st); break;
+    case SMRF_SURFACE_LAPLACE: e = launch_surface<T, SMRF_SURFACE_LAPLACE>(a, gy, st); break;
+    case SMRF_SURFACE_ESRI: e = launch_surface<T, SMRF_SURFACE_ESRI>(a, gy, st); break;
+    case SMRF_SURFACE_ZT: e = launch_surface<T, SMRF_SURFACE_ZT>(a, gy, st); break;
+    case SMRF_SURFACE_EVANS: e = launch_surface<T, SMRF_SURFACE_EVANS>(a, gy, st); break;
+    default: e = launch_surface<T, SMRF_SURFACE_WG>(a, gy, st); break;
   }
   SMRF_HIP_CHECK(e);
   return SMRF_OK;

@@ -2,7 +2,7 @@
 // map pssm() of the notebook workflows (neilpy.py:846-867).
 #include <algorithm>
 
-#include "smrf_common.h"
+#include "raster_stencil.h"
 
 namespace {
 
@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void pssm_kernel(const double* __restrict__ Z,
                                                    int cols, double h, double ve) {
   const long long n = (long long)rows * cols;
   const double h2 = 2.0 * h;
-  const double deg = 180.0 / 3.14159265358979323846;     // np.rad2deg multiplies by 180/pi
+  const double deg = smrf::Consts<double>::rad2deg;
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
     const int r = (int)(i / cols), c = (int)(i - (long long)r * cols);
     double gy, gx;

@@ -10,18 +10,15 @@
 // steps k <= H read LDS and larger steps read global memory.  Direct path: every sample reads global memory.  The
 // arithmetic is the same code in both, so both give the same bits.
 #include <algorithm>
-#include <cmath>
 #include <utility>
 
-#include "smrf_common.h"
+#include "raster_stencil.h"
 
 namespace {
 
 constexpr int TX = 64, TY = 8;
-constexpr double kHalfPi = 3.14159265358979323846 / 2;           // np.pi / 2
-constexpr double kRad2Deg = 180.0 / 3.14159265358979323846;      // np.rad2deg multiplies by 180/pi
-constexpr int kDR[8] = {-1, -1, -1, 0, 1, 1, 1, 0};             // ashift's directions, neilpy.py:1290-1307
-constexpr int kDC[8] = {-1, 0, 1, 1, 1, 0, -1, -1};
+using smrf::kDC, smrf::kDR;
+constexpr double kHalfPi = smrf::Consts<double>::half_pi, kRad2Deg = smrf::Consts<double>::rad2deg;
 
 template <typename T>
 struct RayArgs {
@@ -194,8 +191,8 @@ __global__ __launch_bounds__(TX* TY) void rays_kernel(RayArgs<T> a) {
 }
 
 template <typename T, int MODE>
-hipError_t launch_mode(const RayArgs<T>& a, bool tiled, hipStream_t st) {
-  const dim3 grid((a.cols + TX - 1) / TX, (a.rows + TY - 1) / TY), block(TX, TY);
+hipError_t launch_mode(const RayArgs<T>& a, bool tiled, unsigned gy, hipStream_t st) {
+  const dim3 grid((a.cols + TX - 1) / TX, gy), block(TX, TY);
   if (tiled) {
     const size_t lds = (size_t)(TX + 2 * a.halo) * (TY + 2 * a.halo) * sizeof(T);
     hipLaunchKernelGGL((rays_kernel<T, MODE, true>), grid, block, lds, st, a);
@@ -210,17 +207,18 @@ int terrain_rays(const T* d_Z, int rows, int cols, int mode, const int* d_steps,
                  const double* d_dist, int nsteps, int max_step, const int* d_neighbors, int n_neighbors,
                  int dir_mask, double threshold, int options, const void* d_lut, void* d_out0, void* d_out1,
                  void* d_out2, int impl, void* stream) {
-  if (rows < 0 || cols < 0 || nsteps < 0) return smrf_fail(SMRF_E_ARG, "negative size");
+  if (int rc = smrf::check_size(rows, cols, nsteps)) return rc;
   if (mode < SMRF_TERRAIN_OPENNESS || mode > SMRF_TERRAIN_TERNARY) return smrf_fail(SMRF_E_ARG, "unknown mode %d", mode);
   if (impl < SMRF_TERRAIN_IMPL_AUTO || impl > SMRF_TERRAIN_IMPL_DIRECT) return smrf_fail(SMRF_E_ARG, "unknown impl %d", impl);
-  if ((long long)rows * cols == 0) return SMRF_OK;
+  if (smrf::empty_raster(rows, cols)) return SMRF_OK;
   if (!d_Z || (nsteps > 0 && (!d_steps || !d_flags || !d_dist))) return smrf_fail(SMRF_E_ARG, "null pointer");
   if (mode != SMRF_TERRAIN_COUNT && !d_out0) return smrf_fail(SMRF_E_ARG, "null output");
   if (mode == SMRF_TERRAIN_OPENNESS && (n_neighbors < 1 || !d_neighbors))
     return smrf_fail(SMRF_E_ARG, "openness needs a non-empty neighbors list");
   if (mode == SMRF_TERRAIN_COUNT && d_out2 && !d_lut) return smrf_fail(SMRF_E_ARG, "geomorphons need the 9 x 9 table");
   if (dir_mask < 0 || dir_mask > 255) return smrf_fail(SMRF_E_ARG, "dir_mask out of range");
-  if ((rows + TY - 1) / TY > 65535) return smrf_fail(SMRF_E_ARG, "%d rows exceed the launch grid", rows);
+  unsigned gy = 0;
+  if (int rc = smrf::grid_rows(rows, TY, gy)) return rc;
   RayArgs<T> a{d_Z, rows, cols, d_steps, d_flags, d_dist, nsteps, 0, d_neighbors, n_neighbors, dir_mask,
                threshold, options, d_lut, d_out0, d_out1, d_out2};
   const int cap = sizeof(T) == 8 ? SMRF_TERRAIN_HALO_CAP_F64 : SMRF_TERRAIN_HALO_CAP_F32;
@@ -229,10 +227,10 @@ int terrain_rays(const T* d_Z, int rows, int cols, int mode, const int* d_steps,
   const hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipSuccess;
   switch (mode) {
-    case SMRF_TERRAIN_OPENNESS: e = launch_mode<T, 0>(a, tiled, st); break;
-    case SMRF_TERRAIN_SKYVIEW: e = launch_mode<T, 1>(a, tiled, st); break;
-    case SMRF_TERRAIN_COUNT: e = launch_mode<T, 2>(a, tiled, st); break;
-    default: e = launch_mode<T, 3>(a, tiled, st); break;
+    case SMRF_TERRAIN_OPENNESS: e = launch_mode<T, 0>(a, tiled, gy, st); break;
+    case SMRF_TERRAIN_SKYVIEW: e = launch_mode<T, 1>(a, tiled, gy, st); break;
+    case SMRF_TERRAIN_COUNT: e = launch_mode<T, 2>(a, tiled, gy, st); break;
+    default: e = launch_mode<T, 3>(a, tiled, gy, st); break;
   }
   SMRF_HIP_CHECK(e);
   return SMRF_OK;

@@ -20,9 +20,9 @@ NumPy sums pairwise in the raster's dtype.
 import numpy as np
 
 from . import _lib
-from ._device import device_scoped as _device_scoped, is_tensor as _is_tensor
-from ._xfer import to_host as _d2h
-from .api import _ptr, _stream, _suffix, _to_device, _torch, disk
+from ._device import device_scoped as _device_scoped
+from ._raster import Raster, _ptr, _stream, _torch
+from .api import disk
 
 __all__ = ["focal_convolve", "std", "topographic_position_index", "reduce_peaks", "distance_kernel"]
 
@@ -74,35 +74,21 @@ def _taps(weights):
 # ------------------------------------------------------------------------------------------
 # the launch
 # ------------------------------------------------------------------------------------------
-def _raster(X):
-    Xd = _to_device(X)
-    if Xd.dim() != 2:
-        raise ValueError("expected a 2-D raster")
-    return Xd
+def _workspace(R):
+    n = _lib.load().smrf_focal_workspace_bytes(R.rows, R.cols)
+    return _torch().empty(max(n // 8, 4), dtype=_torch().float64, device=R.t.device)
 
 
-def _out(t, was_tensor):
-    return t if was_tensor else _d2h(t)
-
-
-def _workspace(Xd):
-    rows, cols = Xd.shape
-    n = _lib.load().smrf_focal_workspace_bytes(rows, cols)
-    return _torch().empty(max(n // 8, 4), dtype=_torch().float64, device=Xd.device)
-
-
-def _launch(Xd, mode, weights, outs, S=0.0, sub=None, ws=None, impl=_lib.FOCAL_IMPL_AUTO):
-    lib = _lib.load()
-    rows, cols = Xd.shape
-    if rows == 0 or cols == 0:
-        return
+def _launch(R, mode, weights, outs, S=0.0, sub=None, ws=None, impl=_lib.FOCAL_IMPL_AUTO):
+    """one launch of smrf_focal_* over ``R``, a Raster or (for callers that hold only the plane) a CUDA tensor"""
+    if not isinstance(R, Raster):
+        R = Raster(R)
     w = _weights(weights)
     taps = _taps(w)
-    tab = _torch().from_numpy(taps.view(np.uint8)).to(Xd.device) if len(taps) else None
+    tab = _torch().from_numpy(taps.view(np.uint8)).to(R.t.device) if len(taps) else None
     o = list(outs) + [None] * (2 - len(outs))
-    fn = getattr(lib, "smrf_focal_" + _suffix(Xd))
-    _lib.check(fn(_ptr(Xd), _ptr(sub), rows, cols, mode, _ptr(tab), len(taps), w.shape[0], w.shape[1], float(S),
-                  _ptr(o[0]), _ptr(o[1]), _ptr(ws), 0 if ws is None else ws.numel() * 8, int(impl), _stream()))
+    R.call("focal", _ptr(R.t), _ptr(sub), R.rows, R.cols, mode, _ptr(tab), len(taps), w.shape[0], w.shape[1], float(S),
+           _ptr(o[0]), _ptr(o[1]), _ptr(ws), 0 if ws is None else ws.numel() * 8, int(impl))
     # the tap table is freed by the caching allocator on this stream only after the launch has read it
 
 
@@ -115,16 +101,15 @@ def focal_convolve(X, weights, *, impl=_lib.FOCAL_IMPL_AUTO):
     bit for bit: the non-zero weights are accumulated in float64 in ndimage's order and the sum is rounded to the
     raster's dtype.  ``impl`` forces the tiled or the direct kernel path (same bits)."""
     w = _weights(weights)
-    was_tensor = _is_tensor(X)
-    Xd = _raster(X)
-    out = _torch().empty_like(Xd)
-    _launch(Xd, _lib.FOCAL_SUM, w, [out], impl=impl)
-    return _out(out, was_tensor)
+    R = Raster(X)
+    out = R.empty()
+    _launch(R, _lib.FOCAL_SUM, w, [out], impl=impl)
+    return R.out(out)
 
 
-def _std(Xd, strel, sub=None, impl=_lib.FOCAL_IMPL_AUTO):
-    out = _torch().empty(Xd.shape, dtype=_torch().float64, device=Xd.device)
-    _launch(Xd, _lib.FOCAL_STD, strel, [out], S=float(np.sum(strel)), sub=sub, impl=impl)
+def _std(R, strel, sub=None, impl=_lib.FOCAL_IMPL_AUTO):
+    out = R.empty(_torch().float64)
+    _launch(R, _lib.FOCAL_STD, strel, [out], S=float(np.sum(strel)), sub=sub, impl=impl)
     return out
 
 
@@ -135,9 +120,8 @@ def std(X, strel, *, impl=_lib.FOCAL_IMPL_AUTO):
     arguments and results as neilpy.std."""
     strel = np.asarray(strel)
     _weights(strel)
-    was_tensor = _is_tensor(X)
-    Xd = _raster(X)
-    return _out(_std(Xd, strel, impl=impl), was_tensor)
+    R = Raster(X)
+    return R.out(_std(R, strel, impl=impl))
 
 
 @_device_scoped
@@ -151,16 +135,14 @@ def topographic_position_index(X, radius=1, standardize=True, *, impl=_lib.FOCAL
     strel = np.ones((3, 3), dtype=np.uint8) if radius == 1 else disk(radius)
     strel[radius, radius] = 0
     strel = strel / np.sum(strel)
-    was_tensor = _is_tensor(X)
-    Xd = _raster(X)
-    out = _torch().empty_like(Xd)
-    if Xd.numel():
-        ws = _workspace(Xd)
-        _launch(Xd, _lib.FOCAL_TPI, strel, [out], ws=ws, impl=impl)
+    R = Raster(X)
+    out = R.empty()
+    if R.t.numel():
+        ws = _workspace(R)
+        _launch(R, _lib.FOCAL_TPI, strel, [out], ws=ws, impl=impl)
         if standardize:
-            fn = getattr(_lib.load(), "smrf_focal_divide_" + _suffix(Xd))
-            _lib.check(fn(_ptr(out), out.numel(), _ptr(ws[2:]), _stream()))
-    return _out(out, was_tensor)
+            R.call("focal_divide", _ptr(out), out.numel(), _ptr(ws[2:]))
+    return R.out(out)
 
 
 @_device_scoped
@@ -173,17 +155,13 @@ def reduce_peaks(Z, radius, blend_rate=2, kernel_rate='auto', *, impl=_lib.FOCAL
     strel = distance_kernel(radius, method='distance')
     strel = 1 - (strel / np.max(strel))
     strel = strel ** kernel_rate
-    was_tensor = _is_tensor(Z)
-    Zd = _raster(Z)
-    torch = _torch()
-    out = torch.empty(Zd.shape, dtype=torch.float64, device=Zd.device)
-    if Zd.numel():
-        lib = _lib.load()
-        M = torch.empty_like(Zd)
-        _launch(Zd, _lib.FOCAL_SUM, strel / np.sum(strel), [M], impl=impl)
-        STD = _std(Zd, strel, sub=M, impl=impl)
-        ws = _workspace(Zd)
-        _lib.check(lib.smrf_focal_minmax_f64(_ptr(STD), STD.numel(), _ptr(ws), ws.numel() * 8, _stream()))
-        fn = getattr(lib, "smrf_focal_mix_" + _suffix(Zd))
-        _lib.check(fn(_ptr(Zd), _ptr(M), _ptr(STD), _ptr(ws), float(blend_rate), _ptr(out), out.numel(), _stream()))
-    return _out(out, was_tensor)
+    R = Raster(Z)
+    out = R.empty(_torch().float64)
+    if R.t.numel():
+        M = R.empty()
+        _launch(R, _lib.FOCAL_SUM, strel / np.sum(strel), [M], impl=impl)
+        STD = _std(R, strel, sub=M, impl=impl)
+        ws = _workspace(R)
+        _lib.check(_lib.load().smrf_focal_minmax_f64(_ptr(STD), STD.numel(), _ptr(ws), ws.numel() * 8, _stream()))
+        R.call("focal_mix", _ptr(R.t), _ptr(M), _ptr(STD), _ptr(ws), float(blend_rate), _ptr(out), out.numel())
+    return R.out(out)

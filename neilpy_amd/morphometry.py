@@ -16,10 +16,8 @@ process's ``np.seterr`` state is left alone.
 """
 import numpy as np
 
-from . import _lib
-from ._device import device_scoped as _device_scoped, is_tensor as _is_tensor
-from ._xfer import to_host as _d2h
-from .api import _ptr, _stream, _suffix, _to_device, _torch
+from ._device import device_scoped as _device_scoped
+from ._raster import Raster, _ptr, _pyfloat, _torch
 
 __all__ = ["scaled_morphometry", "vip_score", "ashift", "triangle_height"]
 
@@ -32,26 +30,6 @@ def _stride(n, name):
     if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 1:
         raise ValueError("%s must be an integer >= 1, got %r" % (name, n))
     return min(int(n), _INT_MAX)    # a stride beyond the raster is "every sample is the cell", whatever its value
-
-
-def _check_2d(Z):
-    if len(np.shape(Z)) != 2:
-        raise ValueError("expected a 2-D raster")
-
-
-def _raster(Z):
-    Zd = _to_device(Z)
-    if Zd.dim() != 2:
-        raise ValueError("expected a 2-D raster")
-    return Zd
-
-
-def _empty(Zd, dtype=None):
-    return _torch().empty(Zd.shape, dtype=dtype or Zd.dtype, device=Zd.device)
-
-
-def _out(t, was_tensor):
-    return t if was_tensor else _d2h(t)
 
 
 # ------------------------------------------------------------------------------------------
@@ -87,17 +65,13 @@ def scaled_morphometry(X, cellsize=1, lookup_pixels=1, *, outputs=None):
             if k not in KEYS:
                 raise ValueError("unknown output %r (one of %s)" % (k, list(KEYS)))
         want = tuple(k for k in KEYS if k in asked)
-    _check_2d(X)
-    L = float(cellsize) * int(lookup_pixels)
+    L = _pyfloat(cellsize) * int(lookup_pixels)
     div = (6 * L ** 2, 3 * L ** 2, 4 * L ** 2, 6 * L)
-    was_tensor = _is_tensor(X)
-    Zd = _raster(X)
-    planes = {k: _empty(Zd) for k in want}
-    rows, cols = Zd.shape
-    if rows and cols and want:
-        fn = getattr(_lib.load(), "smrf_morphometry_" + _suffix(Zd))
-        _lib.check(fn(_ptr(Zd), rows, cols, n, *div, *[_ptr(planes.get(k)) for k in KEYS], _stream()))
-    return {k: _out(planes[k], was_tensor) for k in want}
+    R = Raster(X)
+    planes = {k: R.empty() for k in want}
+    if want:
+        R.call("morphometry", _ptr(R.t), R.rows, R.cols, n, *div, *[_ptr(planes.get(k)) for k in KEYS])
+    return {k: R.out(planes[k]) for k in want}
 
 
 @_device_scoped
@@ -105,19 +79,14 @@ def vip_score(Z, cellsize=1):
     """"Very important points" score: the mean over the four lines through a cell (two axes, two diagonals) of the
     cell's height above the line joining its two neighbours (``triangle_height``).  float64, of Z's shape.  Same
     arguments and results as neilpy.vip_score."""
-    _check_2d(Z)
-    cs = float(cellsize)
+    cs = _pyfloat(cellsize)
     dlist = np.array([np.sqrt(2), 1])
     x = [dlist[k] * cs for k in (0, 1)]
     b2 = [(2 * v) ** 2 for v in x]          # a NumPy float64 scalar power: C pow, as the reference's
-    was_tensor = _is_tensor(Z)
-    Zd = _raster(Z)
-    H = _empty(Zd, _torch().float64)
-    rows, cols = Zd.shape
-    if rows and cols:
-        fn = getattr(_lib.load(), "smrf_vip_" + _suffix(Zd))
-        _lib.check(fn(_ptr(Zd), rows, cols, float(x[0]), float(x[1]), float(b2[0]), float(b2[1]), _ptr(H), _stream()))
-    return _out(H, was_tensor)
+    R = Raster(Z)
+    H = R.empty(_torch().float64)
+    R.call("vip", _ptr(R.t), R.rows, R.cols, float(x[0]), float(x[1]), float(b2[0]), float(b2[1]), _ptr(H))
+    return R.out(H)
 
 
 @_device_scoped
@@ -126,13 +95,8 @@ def ashift(surface, direction, n=1):
     clockwise to 7 left), or itself where that neighbour is off the raster; any other direction is a plain copy.  Same
     arguments and results as neilpy.ashift."""
     n = _stride(n, "n")
-    _check_2d(surface)
     d = next((k for k in range(8) if direction == k), -1)
-    was_tensor = _is_tensor(surface)
-    Zd = _raster(surface)
-    out = _empty(Zd)
-    rows, cols = Zd.shape
-    if rows and cols:
-        fn = getattr(_lib.load(), "smrf_ashift_" + _suffix(Zd))
-        _lib.check(fn(_ptr(Zd), rows, cols, d, n, _ptr(out), _stream()))
-    return _out(out, was_tensor)
+    R = Raster(surface)
+    out = R.empty()
+    R.call("ashift", _ptr(R.t), R.rows, R.cols, d, n, _ptr(out))
+    return R.out(out)

@@ -18,32 +18,21 @@ import numpy as np
 
 from . import _lib
 from ._device import device_scoped as _device_scoped, is_tensor as _is_tensor
-from ._xfer import to_host as _d2h
-from .api import _ptr, _stream, _suffix, _to_device, _torch
+from ._raster import Raster, _need_2d, _ptr, _stream, _torch
 
 __all__ = ["inpaint_nearest", "nearest_source"]
 
 
-def _transform(Xd, out, want_index, want_dist):
-    """one run of the kernels over the contiguous float32 / float64 CUDA raster ``Xd``: values into ``out`` (``Xd``
-    itself for an in-place fill, or None); returns the flat int64 index plane and the uint32 squared distances asked for"""
+def _transform(R, out, want_index, want_dist):
+    """one run of the kernels over the raster ``R``: values into ``out`` (``R.t`` itself for an in-place fill, or
+    None); returns the flat int64 index plane and the uint32 squared distances asked for"""
     torch = _torch()
-    lib = _lib.load()
-    rows, cols = Xd.shape
-    index = torch.empty((rows, cols), dtype=torch.int64, device=Xd.device) if want_index else None
-    dist2 = torch.empty((rows, cols), dtype=torch.int32, device=Xd.device) if want_dist else None   # unsigned bits
-    if rows == 0 or cols == 0:
-        return index, dist2
-    nbytes = lib.smrf_nearest_workspace_bytes(rows, cols, Xd.element_size())
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=Xd.device)
-    fn = getattr(lib, "smrf_nearest_" + _suffix(Xd))
-    _lib.check(fn(_ptr(Xd), _ptr(out), _ptr(index), _ptr(dist2), rows, cols, _ptr(ws), nbytes, _stream()))
+    index = R.empty(torch.int64) if want_index else None
+    dist2 = R.empty(torch.int32) if want_dist else None   # unsigned bits
+    nbytes = _lib.load().smrf_nearest_workspace_bytes(R.rows, R.cols, R.t.element_size())
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=R.t.device)
+    R.call("nearest", _ptr(R.t), _ptr(out), _ptr(index), _ptr(dist2), R.rows, R.cols, _ptr(ws), nbytes)
     return index, dist2
-
-
-def _need_2d(shape):
-    if len(shape) != 2:
-        raise ValueError("expected a 2-D raster")
 
 
 @_device_scoped
@@ -52,32 +41,31 @@ def inpaint_nearest(X):
     ``X``.  Same argument and result as neilpy.inpaint_nearest; equally near cells are decided by lowest row, then
     lowest column.  A raster without a finite cell, and a dtype that cannot hold a hole, come back unchanged."""
     torch = _torch()
+    if _is_tensor(X) or isinstance(X, np.ndarray):
+        _need_2d(X)
     _lib.require_gpu()
     if _is_tensor(X):
-        _need_2d(tuple(X.shape))
         if X.dtype not in (torch.float32, torch.float64):
             if X.dtype.is_floating_point:
                 raise TypeError("inpaint_nearest fills float32 and float64 tensors")
             return X                                          # no holes in an integer or bool raster
-        if X.is_cuda and X.is_contiguous():
-            _transform(X, X, False, False)
-        else:
-            work = _to_device(X)
-            if work.data_ptr() == X.data_ptr():               # contiguous() of a contiguous view
-                work = work.clone()
-            _transform(work, work, False, False)
-            X.copy_(work)
+        R = Raster(X)
+        in_place = X.is_cuda and X.is_contiguous()            # R.t is X's own memory
+        if not in_place and R.t.data_ptr() == X.data_ptr():   # contiguous() of a contiguous view
+            R.t = R.t.clone()
+        _transform(R, R.t, False, False)
+        if not in_place:
+            X.copy_(R.t)
         return X
     if not isinstance(X, np.ndarray):
         raise TypeError("inpaint_nearest writes into its argument: pass a NumPy array or a tensor")
-    _need_2d(X.shape)
     if X.dtype.kind != 'f':
         return X                                              # as the reference: np.isfinite is true everywhere
     if X.dtype not in (np.float32, np.float64) and X.dtype != np.float16:
         raise TypeError("inpaint_nearest fills float16, float32 and float64 arrays")
-    work = _to_device(X)                                      # float16 is widened to float64: exact both ways
-    _transform(work, work, False, False)
-    X[...] = _d2h(work)
+    R = Raster(X)                                             # float16 is widened to float64: exact both ways
+    _transform(R, R.t, False, False)
+    X[...] = R.out(R.t)
     return X
 
 
@@ -91,16 +79,14 @@ def nearest_source(X, return_distances=True, return_indices=True):
     if not return_distances and not return_indices:
         raise ValueError("at least one of return_distances / return_indices must be True")
     torch = _torch()
-    was_tensor = _is_tensor(X)
-    Xd = _to_device(X)
-    _need_2d(tuple(Xd.shape))
-    rows, cols = Xd.shape
-    index, dist2 = _transform(Xd, None, bool(return_indices), bool(return_distances))
-    dist = torch.empty((rows, cols), dtype=torch.float64, device=Xd.device) if return_distances else None
-    rc = torch.empty((2, rows, cols), dtype=torch.int64, device=Xd.device) if return_indices else None
+    R = Raster(X)
+    rows, cols = R.rows, R.cols
+    index, dist2 = _transform(R, None, bool(return_indices), bool(return_distances))
+    dist = R.empty(torch.float64) if return_distances else None
+    rc = torch.empty((2, rows, cols), dtype=torch.int64, device=R.t.device) if return_indices else None
     if rows and cols:
         _lib.check(_lib.load().smrf_nearest_planes(_ptr(index), _ptr(dist2), rows * cols, cols, _ptr(dist),
                                                    _ptr(rc[0]) if return_indices else None,
                                                    _ptr(rc[1]) if return_indices else None, _stream()))
-    res = tuple(t if was_tensor else _d2h(t) for t in (dist, rc) if t is not None)
+    res = tuple(R.out(t) for t in (dist, rc) if t is not None)
     return res if len(res) == 2 else res[0]

@@ -23,7 +23,7 @@ import numpy as np
 from . import _lib
 from ._device import device_scoped as _device_scoped, is_tensor as _is_tensor
 from ._xfer import to_host as _d2h
-from .api import _ptr, _stream, _to_device, _torch
+from ._raster import _ptr, _stream, _to_device, _torch
 
 __all__ = ["nearest_points", "chamfer_distance"]
 

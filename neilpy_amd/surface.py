@@ -20,9 +20,8 @@ its window differences by a product where the reference's per-cell callback call
 import numpy as np
 
 from . import _lib
-from ._device import device_scoped as _device_scoped, is_tensor as _is_tensor
-from ._xfer import to_host as _d2h
-from .api import _ptr, _stream, _suffix, _to_device, _torch
+from ._device import device_scoped as _device_scoped
+from ._raster import Raster, _ptr, _pyfloat as _f, _torch
 
 __all__ = ["slope", "aspect", "hillshade", "multiple_illumination", "esri_slope", "curvature", "esri_curvature",
            "zevenbergen_and_thorne_curvature", "evans_curvature", "wilson_gallant_curvature", "z_factor"]
@@ -61,21 +60,9 @@ def _angle_lists(zeniths, azimuths):
     return zeniths, azimuths
 
 
-def _f(v):
-    """a parameter as a Python float (NumPy scalars included: they would otherwise promote float32 rasters)"""
-    return float(v)
-
-
 # ------------------------------------------------------------------------------------------
 # the launch
 # ------------------------------------------------------------------------------------------
-def _raster(Z):
-    Zd = _to_device(Z)
-    if Zd.dim() != 2:
-        raise ValueError("expected a 2-D raster")
-    return Zd
-
-
 def _need_gradient(Z):
     """np.gradient's size check, made before anything touches the device"""
     shape = tuple(np.shape(Z))
@@ -83,28 +70,15 @@ def _need_gradient(Z):
         raise ValueError(_GRADIENT_MSG)
 
 
-def _launch(Zd, mode, outs, params=(), options=0, angles=None):
-    lib = _lib.load()
-    rows, cols = Zd.shape
-    if rows == 0 or cols == 0:
-        return
+def _launch(R, mode, outs, params=(), options=0, angles=None):
     p = [float(v) for v in params] + [0.0] * (4 - len(params))
     o = list(outs) + [None] * (6 - len(outs))
     tab = None
     if angles is not None:
-        tab = _torch().from_numpy(np.asarray(angles, dtype=np.float64).reshape(-1)).to(Zd.device)
-    fn = getattr(lib, "smrf_surface_" + _suffix(Zd))
-    _lib.check(fn(_ptr(Zd), rows, cols, mode, options, p[0], p[1], p[2], p[3], _ptr(tab),
-                  0 if angles is None else len(angles), *[_ptr(t) for t in o], _stream()))
+        tab = _torch().from_numpy(np.asarray(angles, dtype=np.float64).reshape(-1)).to(R.t.device)
+    R.call("surface", _ptr(R.t), R.rows, R.cols, mode, options, p[0], p[1], p[2], p[3], _ptr(tab),
+           0 if angles is None else len(angles), *[_ptr(t) for t in o])
     # the angle table is freed by the caching allocator on this stream only after the launch has read it
-
-
-def _empty(Zd, dtype=None):
-    return _torch().empty(Zd.shape, dtype=dtype or Zd.dtype, device=Zd.device)
-
-
-def _out(t, was_tensor):
-    return t if was_tensor else _d2h(t)
 
 
 def _check_return_as(return_as, options):
@@ -121,13 +95,12 @@ def slope(Z, cellsize=1, z_factor=1, return_as='degrees'):
     norm, 1 = 100 %).  Same arguments and results as neilpy.slope."""
     _check_return_as(return_as, ('degrees', 'radians', 'percent'))
     _need_gradient(Z)
-    was_tensor = _is_tensor(Z)
-    Zd = _raster(Z)
+    R = Raster(Z)
     h = _f(cellsize) / _f(z_factor)
     opt = {'percent': 0, 'radians': _lib.SURFACE_OPT_RADIANS, 'degrees': _lib.SURFACE_OPT_DEGREES}[return_as]
-    S = _empty(Zd)
-    _launch(Zd, _lib.SURFACE_SLOPE, [S], (h,), opt)
-    return _out(S, was_tensor)
+    S = R.empty()
+    _launch(R, _lib.SURFACE_SLOPE, [S], (h,), opt)
+    return R.out(S)
 
 
 @_device_scoped
@@ -137,11 +110,10 @@ def aspect(Z, return_as='degrees', flat_as='nan'):
     _check_return_as(return_as, ('degrees', 'radians'))
     flat = np.nan if isinstance(flat_as, str) and flat_as == 'nan' else _f(flat_as)
     _need_gradient(Z)
-    was_tensor = _is_tensor(Z)
-    Zd = _raster(Z)
-    A = _empty(Zd)
-    _launch(Zd, _lib.SURFACE_ASPECT, [A], (flat,), _lib.SURFACE_OPT_DEGREES if return_as == 'degrees' else 0)
-    return _out(A, was_tensor)
+    R = Raster(Z)
+    A = R.empty()
+    _launch(R, _lib.SURFACE_ASPECT, [A], (flat,), _lib.SURFACE_OPT_DEGREES if return_as == 'degrees' else 0)
+    return R.out(A)
 
 
 @_device_scoped
@@ -149,13 +121,12 @@ def hillshade(Z, cellsize=1, z_factor=1, zenith=45, azimuth=315, return_uint8=Tr
     """ESRI-style hillshade from slope(radians) and aspect(radians, flat_as=0): uint8 ``round(255 * H)`` (NaN cells
     0), or H as float64 with ``return_uint8=False``.  Same arguments and results as neilpy.hillshade."""
     _need_gradient(Z)
-    was_tensor = _is_tensor(Z)
-    Zd = _raster(Z)
+    R = Raster(Z)
     h = _f(cellsize) / _f(z_factor)
-    H = _empty(Zd, _torch().uint8 if return_uint8 else _torch().float64)
+    H = R.empty(_torch().uint8 if return_uint8 else _torch().float64)
     outs = [H] if return_uint8 else [None, H]
-    _launch(Zd, _lib.SURFACE_HILLSHADE, outs, (h,), angles=[_angle_row(zenith, azimuth)])
-    return _out(H, was_tensor)
+    _launch(R, _lib.SURFACE_HILLSHADE, outs, (h,), angles=[_angle_row(zenith, azimuth)])
+    return R.out(H)
 
 
 @_device_scoped
@@ -165,15 +136,14 @@ def multiple_illumination(Z, cellsize=1, z_factor=1, zeniths=np.array([45]), azi
     results as neilpy.multiple_illumination."""
     zs, azs = _angle_lists(zeniths, azimuths)
     _need_gradient(Z)
-    was_tensor = _is_tensor(Z)
-    Zd = _raster(Z)
-    H = _empty(Zd, _torch().uint8)
+    R = Raster(Z)
+    H = R.empty(_torch().uint8)
     table = [_angle_row(z, a) for z in zs for a in azs]
     if not table:
         H.zero_()
     else:
-        _launch(Zd, _lib.SURFACE_HILLSHADE, [H], (_f(cellsize) / _f(z_factor),), angles=table)
-    return _out(H, was_tensor)
+        _launch(R, _lib.SURFACE_HILLSHADE, [H], (_f(cellsize) / _f(z_factor),), angles=table)
+    return R.out(H)
 
 
 @_device_scoped
@@ -181,31 +151,28 @@ def esri_slope(Z, cellsize=1, z_factor=1, return_as='degrees'):
     """ESRI's 3 x 3 (Horn) slope with ndimage's 'reflect' edges, divided by ``cellsize`` and scaled by ``z_factor``;
     in degrees for return_as='degrees', otherwise the rise over run.  Same arguments and results as neilpy.esri_slope
     (which accepts any other ``return_as`` as "not degrees")."""
-    was_tensor = _is_tensor(Z)
-    Zd = _raster(Z)
-    S = _empty(Zd)
-    _launch(Zd, _lib.SURFACE_HORN, [S], (_f(cellsize), _f(z_factor)),
+    R = Raster(Z)
+    S = R.empty()
+    _launch(R, _lib.SURFACE_HORN, [S], (_f(cellsize), _f(z_factor)),
             _lib.SURFACE_OPT_DEGREES if return_as == 'degrees' else 0)
-    return _out(S, was_tensor)
+    return R.out(S)
 
 
 @_device_scoped
 def curvature(X, cellsize=1):
     """``-100 * laplace(X / cellsize)`` with ndimage's 'reflect' edges.  Same arguments and results as
     neilpy.curvature."""
-    was_tensor = _is_tensor(X)
-    Zd = _raster(X)
-    K = _empty(Zd)
-    _launch(Zd, _lib.SURFACE_LAPLACE, [K], (_f(cellsize),))
-    return _out(K, was_tensor)
+    R = Raster(X)
+    K = R.empty()
+    _launch(R, _lib.SURFACE_LAPLACE, [K], (_f(cellsize),))
+    return R.out(K)
 
 
 def _multi(X, mode, n, params):
-    was_tensor = _is_tensor(X)
-    Zd = _raster(X)
-    outs = [_empty(Zd) for _ in range(n)]
-    _launch(Zd, mode, outs, params)
-    return tuple(_out(t, was_tensor) for t in outs)
+    R = Raster(X)
+    outs = [R.empty() for _ in range(n)]
+    _launch(R, mode, outs, params)
+    return tuple(R.out(t) for t in outs)
 
 
 @_device_scoped

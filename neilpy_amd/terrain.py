@@ -19,8 +19,7 @@ import numpy as np
 
 from . import _lib
 from ._device import device_scoped as _device_scoped, is_tensor as _is_tensor
-from ._xfer import to_host as _d2h
-from .api import _ptr, _stream, _suffix, _to_device, _torch
+from ._raster import Raster, _ptr, _torch
 
 __all__ = ["openness", "skyview_factor", "count_openness", "geomorphons", "ternary_pattern_from_openness",
            "progressive_window", "int2base", "get_lowest_equivalent", "terrain_code_to_geomorphon",
@@ -189,33 +188,19 @@ def _lookup_int(lookup_pixels):
 # ------------------------------------------------------------------------------------------
 # the launch
 # ------------------------------------------------------------------------------------------
-def _rays(Zd, mode, march, outs, neighbors=None, dir_mask=0xFF, threshold=0.0, options=0, lut=None, impl=0):
-    torch = _torch()
-    lib = _lib.load()
-    rows, cols = Zd.shape
-    if rows == 0 or cols == 0:
+def _rays(R, mode, march, outs, neighbors=None, dir_mask=0xFF, threshold=0.0, options=0, lut=None, impl=0):
+    if R.rows == 0 or R.cols == 0:
         return
     if impl not in (_lib.TERRAIN_IMPL_AUTO, _lib.TERRAIN_IMPL_TILED, _lib.TERRAIN_IMPL_DIRECT):
         raise ValueError("impl must be one of 0 (auto), 1 (tiled), 2 (direct)")
-    steps, flags, dist = march.to(Zd.device)
-    nbr = torch.from_numpy(np.asarray(neighbors, dtype=np.int32)).to(Zd.device) if neighbors is not None else None
+    device = R.t.device
+    steps, flags, dist = march.to(device)
+    nbr = _torch().from_numpy(np.asarray(neighbors, dtype=np.int32)).to(device) if neighbors is not None else None
     o = list(outs) + [None] * (3 - len(outs))
-    fn = getattr(lib, "smrf_terrain_rays_" + _suffix(Zd))
-    _lib.check(fn(_ptr(Zd), rows, cols, mode, _ptr(steps), _ptr(flags), _ptr(dist), march.n, march.max_step, _ptr(nbr),
-                  0 if nbr is None else nbr.numel(), dir_mask, float(threshold), options, _ptr(lut), _ptr(o[0]),
-                  _ptr(o[1]), _ptr(o[2]), int(impl), _stream()))
+    R.call("terrain_rays", _ptr(R.t), R.rows, R.cols, mode, _ptr(steps), _ptr(flags), _ptr(dist), march.n,
+           march.max_step, _ptr(nbr), 0 if nbr is None else nbr.numel(), dir_mask, float(threshold), options, _ptr(lut),
+           _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), int(impl))
     # the step tables are freed by the caching allocator on this stream only after the launch has read them
-
-
-def _raster(Z):
-    Zd = _to_device(Z)
-    if Zd.dim() != 2:
-        raise ValueError("expected a 2-D raster")
-    return Zd
-
-
-def _out(t, was_tensor):
-    return t if was_tensor else _d2h(t)
 
 
 # ------------------------------------------------------------------------------------------
@@ -236,13 +221,12 @@ def openness(Z, cellsize=1, lookup_pixels=1, neighbors=np.arange(8), skyview=Fal
         raise ValueError("neighbors must not be empty")
     if not np.issubdtype(nb.dtype, np.integer) or nb.min() < 0 or nb.max() > 7:
         raise ValueError("neighbors must hold directions 0..7 (got %s)" % (list(nb),))
-    was_tensor = _is_tensor(Z)
-    Zd = _raster(Z)
-    out = torch.empty(Zd.shape, dtype=torch.float64, device=Zd.device)
+    R = Raster(Z)
+    out = R.empty(torch.float64)
     march = _March(_as_steps(_lookup_int(lookup_pixels), fast, how_fast), cellsize=cellsize)
     mask = int(np.bitwise_or.reduce(1 << nb.astype(np.int64)))
-    _rays(Zd, _lib.TERRAIN_OPENNESS, march, [out], neighbors=nb, dir_mask=mask, impl=impl)
-    return _out(out, was_tensor)
+    _rays(R, _lib.TERRAIN_OPENNESS, march, [out], neighbors=nb, dir_mask=mask, impl=impl)
+    return R.out(out)
 
 
 @_device_scoped
@@ -251,16 +235,15 @@ def skyview_factor(Z, cellsize=1, lookup_pixels=1, *, impl=_lib.TERRAIN_IMPL_AUT
 
     Same arguments and results as neilpy.skyview_factor (float64); a ray stops at the raster's edge."""
     torch = _torch()
-    was_tensor = _is_tensor(Z)
-    Zd = _raster(Z)
-    out = torch.empty(Zd.shape, dtype=torch.float64, device=Zd.device)
+    R = Raster(Z)
+    out = R.empty(torch.float64)
     L = _lookup_int(lookup_pixels)
     march = _March(list(range(1, L + 1)), cellsize=cellsize)      # python ints, as the reference's range (:1370)
-    _rays(Zd, _lib.TERRAIN_SKYVIEW, march, [out], impl=impl)
-    return _out(out, was_tensor)
+    _rays(R, _lib.TERRAIN_SKYVIEW, march, [out], impl=impl)
+    return R.out(out)
 
 
-def _counts(Zd, cellsize, lookup_pixels, threshold_angle, fast, how_fast, want_counts, want_geo, enhance, impl):
+def _counts(R, cellsize, lookup_pixels, threshold_angle, fast, how_fast, want_counts, want_geo, enhance, impl):
     torch = _torch()
     L = _lookup_int(lookup_pixels)
     small = ()
@@ -269,11 +252,11 @@ def _counts(Zd, cellsize, lookup_pixels, threshold_angle, fast, how_fast, want_c
         Lsm = max(Lsm, 4)
         small = list(np.arange(1, Lsm + 1))
     march = _March(_as_steps(L, fast, how_fast), small, cellsize=cellsize)
-    mk = lambda: torch.empty(Zd.shape, dtype=torch.uint8, device=Zd.device)  # noqa: E731
+    mk = lambda: R.empty(torch.uint8)  # noqa: E731
     pos, neg = (mk(), mk()) if want_counts else (None, None)
     geo = mk() if want_geo else None
-    lut = _device_table("geo9", GEOMORPHON_TABLE, Zd.device) if want_geo else None
-    _rays(Zd, _lib.TERRAIN_COUNT, march, [pos, neg, geo], threshold=threshold_angle,
+    lut = _device_table("geo9", GEOMORPHON_TABLE, R.t.device) if want_geo else None
+    _rays(R, _lib.TERRAIN_COUNT, march, [pos, neg, geo], threshold=threshold_angle,
           options=2 if enhance else 0, lut=lut, impl=impl)
     return pos, neg, geo
 
@@ -283,10 +266,9 @@ def count_openness(Z, cellsize, lookup_pixels, threshold_angle, fast=False, how_
                    impl=_lib.TERRAIN_IMPL_AUTO):
     """``(num_pos, num_neg)`` (uint8): per cell, the directions whose positive minus negative openness is above
     ``threshold_angle`` / below ``-threshold_angle`` degrees.  Same arguments and results as neilpy.count_openness."""
-    was_tensor = _is_tensor(Z)
-    Zd = _raster(Z)
-    pos, neg, _ = _counts(Zd, cellsize, lookup_pixels, threshold_angle, fast, how_fast, True, False, False, impl)
-    return _out(pos, was_tensor), _out(neg, was_tensor)
+    R = Raster(Z)
+    pos, neg, _ = _counts(R, cellsize, lookup_pixels, threshold_angle, fast, how_fast, True, False, False, impl)
+    return R.out(pos), R.out(neg)
 
 
 @_device_scoped
@@ -298,11 +280,10 @@ def geomorphons(Z, cellsize=1, lookup_pixels=1, threshold_angle=1, enhance=False
     ``max(lookup_pixels // 4, 4)`` steps and applies the reference's correction of forms (:1640-1649); both counts
     come from one march.
     """
-    was_tensor = _is_tensor(Z)
-    Zd = _raster(Z)
+    R = Raster(Z)
     enh = enhance == True and lookup_pixels > 16  # noqa: E712  (the reference's own test, :1640)
-    _, _, geo = _counts(Zd, cellsize, lookup_pixels, threshold_angle, fast, how_fast, False, True, enh, impl)
-    return _out(geo, was_tensor)
+    _, _, geo = _counts(R, cellsize, lookup_pixels, threshold_angle, fast, how_fast, False, True, enh, impl)
+    return R.out(geo)
 
 
 @_device_scoped
@@ -313,11 +294,10 @@ def ternary_pattern_from_openness(Z, cellsize=1, lookup_pixels=1, threshold_angl
     rotation / reflection equivalent.  Same arguments and results as neilpy.ternary_pattern_from_openness under
     NumPy 2 (whose type promotion turns the reference's uint16 accumulator into int64)."""
     torch = _torch()
-    was_tensor = _is_tensor(Z)
-    Zd = _raster(Z)
-    out = torch.empty(Zd.shape, dtype=torch.int64, device=Zd.device)
+    R = Raster(Z)
+    out = R.empty(torch.int64)
     march = _March(_as_steps(_lookup_int(lookup_pixels)), cellsize=cellsize)
-    lut = _device_table("lowest", _lowest_table().astype(np.int64), Zd.device) if lowest else None
-    _rays(Zd, _lib.TERRAIN_TERNARY, march, [out], threshold=threshold_angle,
+    lut = _device_table("lowest", _lowest_table().astype(np.int64), R.t.device) if lowest else None
+    _rays(R, _lib.TERRAIN_TERNARY, march, [out], threshold=threshold_angle,
           options=1 if use_negative_openness else 0, lut=lut, impl=impl)
-    return _out(out, was_tensor)
+    return R.out(out)

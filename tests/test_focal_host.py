@@ -4,13 +4,13 @@ the tolerance that the GPU test allows standardised TPI."""
 import inspect
 import json
 import math
-import os
 
 import numpy as np
 import pytest
 
 import focal_numpy as fn
-from conftest import GOLDEN, golden
+from conftest import golden
+from family_checks import assert_no_scratch, device_asm, same_bits, signatures_match
 
 
 def cases():
@@ -25,11 +25,6 @@ def restate(G, c):
     if c["fn"] == "std":
         return fn.std(X, G["k_" + c["kernel"]])
     return getattr(fn, c["fn"])(X, **c["kw"])
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b, equal_nan=True) and \
-        np.array_equal(np.signbit(a[a == 0]), np.signbit(b[b == 0]))
 
 
 def test_golden_covers_the_issue_cases():
@@ -97,16 +92,8 @@ def test_distance_kernel_equals_golden_and_needs_no_gpu():
 
 def test_signatures_match_the_reference():
     import neilpy_amd
-    want = json.load(open(os.path.join(GOLDEN, "focal_signatures.json")))
+    want = signatures_match("focal_signatures.json", 4)
     assert set(want) == {"std", "topographic_position_index", "reduce_peaks", "distance_kernel"}
-    for name, params in want.items():
-        got = list(inspect.signature(getattr(neilpy_amd, name)).parameters.values())
-        for i, p in enumerate(params):
-            g = got[i]
-            assert (g.name, g.kind.name) == (p["name"], p["kind"]), (name, i, g, p)
-            assert (None if g.default is inspect.Parameter.empty else repr(g.default)) == p["default"], (name, g, p)
-        for g in got[len(params):]:
-            assert g.kind is inspect.Parameter.KEYWORD_ONLY, (name, g)
     got = list(inspect.signature(neilpy_amd.focal_convolve).parameters.values())
     assert [g.name for g in got[:2]] == ["X", "weights"]
     assert all(g.kind is inspect.Parameter.KEYWORD_ONLY for g in got[2:])
@@ -223,18 +210,9 @@ def test_focal_kernels_compile_without_scratch(tmp_path):
     """every kernel of csrc/focal.hip keeps its state in registers, and no fused multiply-add reaches the tap loop's
     sums: the only fp64 FMAs are those of the divide, sqrt and pow expansions of the tails (no GPU needed)"""
     import re
-    import subprocess
-    from neilpy_amd.build import CSRC, FLAGS, hipcc
-    out = str(tmp_path / "focal.s")
-    cmd = [hipcc()] + [f for f in FLAGS if f != "-fPIC"] + ["--offload-device-only", "-S",
-                                                           os.path.join(CSRC, "focal.hip"), "-o", out]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    text = open(out).read()
-    kernels = dict(re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", text, re.S))
+    text, kernels = device_asm("focal", tmp_path)
     assert len(kernels) == 24       # focal: 2 dtypes x 4 modes x {tiled, direct}; 2 TPI reduce, 2 divide, 2 min / max, 2 mix
-    for name, body in kernels.items():
-        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)) == 0, name
+    assert_no_scratch(text, kernels)
     # SUM / SUM_SQ instances have no tail: not one FMA in them
     bodies = dict(re.findall(r"^(_ZN\S*focal_kernel\S*):[^\n]*\n(.*?)s_endpgm", text, re.S | re.M))
     plain = [b for n, b in bodies.items() if re.search(r"focal_kernelI[fd]Li[01]ELb[01]E", n)]

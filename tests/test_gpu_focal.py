@@ -17,7 +17,7 @@ from conftest import golden
 
 pytestmark = pytest.mark.gpu
 
-ULPS = 8          # tests/test_gpu_surface.py's
+ULPS = 8          # tests/family_checks.py's
 AUTO, TILED, DIRECT = 0, 1, 2
 
 

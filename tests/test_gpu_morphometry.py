@@ -4,7 +4,7 @@ device-resident route from smrf().
 
 Outputs built from + - * / and sqrt only are bit-exact: K, K_cross, K_long, K_tan, all of vip_score, and ashift.  S,
 K_profile and K_plan go through atan or pow (the device's are not glibc's) and match within ULPS units in the last place
-of the output dtype, with NaN and inf positions identical: the rule and the constant of tests/test_gpu_surface.py.  A
+of the output dtype, with NaN and inf positions identical: the rule and the constant of tests/family_checks.py.  A
 (atan2, then 270 - a, mod 360) matches within ULPS ulps of itself plus ULPS ulps of 360, on the circular difference
 min(|d|, 360 - |d|): the wrap sits at atan2 = -90 degrees."""
 import json
@@ -14,10 +14,10 @@ import pytest
 
 import morphometry_numpy as mn
 from conftest import golden, load_sample
+from family_checks import assert_close, assert_exact
 
 pytestmark = pytest.mark.gpu
 
-ULPS = 8
 EXACT = ("K", "K_cross", "K_long", "K_tan")
 CLOSE = ("S", "K_profile", "K_plan")
 
@@ -25,27 +25,6 @@ CLOSE = ("S", "K_profile", "K_plan")
 def _na():
     import neilpy_amd
     return neilpy_amd
-
-
-def assert_exact(got, want, ctx):
-    assert got.dtype == want.dtype and got.shape == want.shape, (ctx, got.dtype, want.dtype)
-    assert np.array_equal(got, want, equal_nan=True), (ctx, int(np.sum(~((got == want) | (np.isnan(got) & np.isnan(want))))))
-
-
-def assert_close(got, want, scale, ctx, circular=None):
-    """tests/test_gpu_surface.py::assert_close; ``circular``: the period of an angle, compared on the shorter arc"""
-    assert got.dtype == want.dtype and got.shape == want.shape, (ctx, got.dtype, want.dtype)
-    assert np.array_equal(np.isnan(got), np.isnan(want)), ctx
-    inf = np.isinf(want)
-    assert np.array_equal(np.isinf(got), inf) and np.array_equal(got[inf], want[inf]), ctx
-    fin = np.isfinite(want)
-    if fin.any():
-        tol = ULPS * (np.spacing(np.abs(want[fin]).astype(want.dtype)).astype(np.float64) +
-                      float(np.spacing(want.dtype.type(scale))))
-        err = np.abs(got[fin].astype(np.float64) - want[fin].astype(np.float64))
-        if circular is not None:
-            err = np.minimum(err, circular - err)
-        assert np.all(err <= tol), (ctx, float(np.max(err / tol)))
 
 
 def compare_morphometry(got, want, ctx):

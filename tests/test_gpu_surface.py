@@ -13,10 +13,10 @@ import pytest
 
 import surface_numpy as sn
 from conftest import golden, load_sample
+from family_checks import assert_close
 
 pytestmark = pytest.mark.gpu
 
-ULPS = 8
 MARGIN = 1e-9
 MARGIN_F32 = 1e-4
 
@@ -61,22 +61,6 @@ def margin_of(fn, Z, kw):
         return sn.half_margin(sn.hillshade_value(Z, **kw),
                               sn.flat_cells(Z, kw.get("cellsize", 1), kw.get("z_factor", 1)))
     return sn.multiple_illumination(Z, **kw, return_margin=True)[1]
-
-
-def assert_close(got, want, scale, ctx, unit=None):
-    """``unit``: the dtype whose ulp of ``scale`` is allowed (hillshade's float64 shade of a float32 raster carries
-    float32 cos / sin)"""
-    assert got.dtype == want.dtype and got.shape == want.shape, (ctx, got.dtype, want.dtype)
-    assert np.array_equal(np.isnan(got), np.isnan(want)), ctx
-    inf = np.isinf(want)
-    assert np.array_equal(np.isinf(got), inf) and np.array_equal(got[inf], want[inf]), ctx
-    fin = np.isfinite(want)
-    if fin.any():
-        unit = np.dtype(unit or want.dtype)
-        tol = ULPS * (np.spacing(np.abs(want[fin]).astype(want.dtype)).astype(np.float64) +
-                      float(np.spacing(unit.type(scale))))
-        err = np.abs(got[fin].astype(np.float64) - want[fin].astype(np.float64))
-        assert np.all(err <= tol), (ctx, float(np.max(err / tol)))
 
 
 def compare(fn, Z, kw, got, want):

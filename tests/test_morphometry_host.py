@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 
 import morphometry_numpy as mn
-from conftest import GOLDEN, golden
+from conftest import golden
+from family_checks import same_bits, signatures_match
 
 
 @pytest.fixture(scope="module")
@@ -21,11 +22,6 @@ def G():
 
 def _cases(G):
     return json.loads(str(G["cases"]))
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b, equal_nan=True) and \
-        np.array_equal(np.signbit(a[a == 0]), np.signbit(b[b == 0]))
 
 
 def test_restatement_equals_every_golden(G):
@@ -78,17 +74,8 @@ def test_golden_cases_cover_the_contract(G):
 
 def test_signatures_match_the_reference():
     import neilpy_amd
-    with open(os.path.join(GOLDEN, "morphometry_signatures.json")) as f:
-        want = json.load(f)
+    want = signatures_match("morphometry_signatures.json", 4)
     assert set(want) == {"scaled_morphometry", "vip_score", "ashift", "triangle_height"}
-    for name, params in want.items():
-        got = list(inspect.signature(getattr(neilpy_amd, name)).parameters.values())
-        assert len(got) >= len(params), name
-        for g, p in zip(got, params):
-            assert (g.name, g.kind.name) == (p["name"], p["kind"]), (name, g, p)
-            assert (None if g.default is inspect.Parameter.empty else repr(g.default)) == p["default"], (name, g, p)
-        for g in got[len(params):]:
-            assert g.kind is inspect.Parameter.KEYWORD_ONLY, (name, g)
     assert "outputs" in inspect.signature(neilpy_amd.scaled_morphometry).parameters
 
 

@@ -6,14 +6,14 @@ import inspect
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 from scipy import ndimage
 
 import nearest_numpy as nn
-from conftest import GOLDEN, ROOT, golden
+from conftest import ROOT, golden
+from family_checks import assert_no_scratch, device_asm, signatures_match
 
 
 @pytest.fixture(scope="module")
@@ -147,17 +147,7 @@ def test_restatement_tie_rule():
 
 def test_signature_matches_the_reference():
     import neilpy_amd
-    with open(os.path.join(GOLDEN, "nearest_signatures.json")) as f:
-        want = json.load(f)
-    assert list(want) == ["inpaint_nearest"]
-    for name, params in want.items():
-        got = list(inspect.signature(getattr(neilpy_amd, name)).parameters.values())
-        assert len(got) >= len(params), name
-        for g, p in zip(got, params):
-            assert (g.name, g.kind.name) == (p["name"], p["kind"]), (name, g, p)
-            assert (None if g.default is inspect.Parameter.empty else repr(g.default)) == p["default"], (name, g, p)
-        for g in got[len(params):]:
-            assert g.kind is inspect.Parameter.KEYWORD_ONLY, (name, g)
+    assert list(signatures_match("nearest_signatures.json", 1)) == ["inpaint_nearest"]
     ns = inspect.signature(neilpy_amd.nearest_source).parameters
     assert list(ns) == ["X", "return_distances", "return_indices"]
     assert ns["return_distances"].default is True and ns["return_indices"].default is True
@@ -201,22 +191,13 @@ def test_no_cpu_fallback():
 def test_nearest_kernels_compile_without_scratch(tmp_path):
     """every kernel of csrc/nearest.hip keeps its state in registers (ScratchSize 0) and decides no winner with an
     atomic (no GPU needed)"""
-    from neilpy_amd.build import CSRC, FLAGS, hipcc
-    out = str(tmp_path / "nearest.s")
-    cmd = [hipcc()] + [f for f in FLAGS if f != "-fPIC"] + ["--offload-device-only", "-S",
-                                                           os.path.join(CSRC, "nearest.hip"), "-o", out]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    text = open(out).read()
-    kernels = dict(re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", text, re.S))
+    text, kernels = device_asm("nearest", tmp_path)
     names = sorted(kernels)
     assert len(names) == 7, names             # mask x 2 dtypes, carry, envelope, lookup x 2 dtypes, planes
     for stem, n in (("nearest_mask_kernel", 2), ("nearest_carry_kernel", 1), ("nearest_envelope_kernel", 1),
                     ("nearest_lookup_kernel", 2), ("nearest_planes_kernel", 1)):
         assert sum(stem in k for k in names) == n, (stem, names)
-    for name, body in kernels.items():
-        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)) == 0, name
-    assert set(re.findall(r"ScratchSize:\s*(\d+)", text)) == {"0"}
+    assert_no_scratch(text, kernels)
     assert not re.search(r"^\s*(global|flat|buffer|ds)_atomic|^\s*ds_(add|min|max|cmpst)", text, re.M)
     env = [b for k, b in kernels.items() if "nearest_envelope_kernel" in k][0]
     assert int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", env).group(1)) == 64 * 65 * 4   # the transposing tile

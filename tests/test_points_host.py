@@ -6,13 +6,13 @@ import inspect
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import points_numpy as pn
 from conftest import ROOT, golden
+from family_checks import assert_no_scratch, device_asm
 
 DIRECTIONS = ("y_to_x", "x_to_y", "bi")
 ABI_NAMES = ("smrf_points_nn_workspace_bytes", "smrf_points_nn_bounds_f64", "smrf_points_nn_build_f64",
@@ -151,24 +151,16 @@ def test_no_cpu_fallback():
 def test_points_kernels_compile_without_scratch(tmp_path):
     """every kernel of csrc/points.hip keeps its state in registers, the squares and sums of the distance stay separate
     instructions, and the only atomics are the sort's integer counters (no GPU needed)"""
-    from neilpy_amd.build import CSRC, FLAGS, hipcc
-    out = str(tmp_path / "points.s")
-    cmd = [hipcc()] + [f for f in FLAGS if f != "-fPIC"] + ["--offload-device-only", "-S",
-                                                           os.path.join(CSRC, "points.hip"), "-o", out]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    text = open(out).read()
-    kernels = dict(re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", text, re.S))
+    text, kernels = device_asm("points", tmp_path)
     names = sorted(kernels)
     assert len(names) == 9, names      # bounds, count, scan x 3, scatter, search x 2 dimensions, sum
     for stem, n in (("points_bounds_kernel", 1), ("points_count_kernel", 1), ("points_scan_", 3),
                     ("points_scatter_kernel", 1), ("points_search_kernel", 2), ("points_sum_kernel", 1)):
         assert sum(stem in k for k in names) == n, (stem, names)
+    assert_no_scratch(text, kernels)
     for name, body in kernels.items():
-        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)) == 0, name
         if "points_search_kernel" in name:
             assert int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", body).group(1)) == 0, name
-    assert set(re.findall(r"ScratchSize:\s*(\d+)", text)) == {"0"}
     atomics = set(re.findall(r"^\s*((?:global|flat|buffer|ds)_atomic\w*)", text, re.M))
     assert atomics and all(re.fullmatch(r"global_atomic_(add|sub)(_u32)?", a) for a in atomics), atomics
     # the search kernels' code: the distance is formed with separate v_mul_f64 / v_add_f64 (the fused multiply-adds that

@@ -2,17 +2,16 @@
 helpers, signatures, ABI exports, the no-fallback rule, the documented deviations and the generated code of
 csrc/surface.hip."""
 import ctypes
-import inspect
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import surface_numpy as sn
-from conftest import GOLDEN, ROOT, golden
+from conftest import ROOT, golden
+from family_checks import assert_no_scratch, device_asm, signatures_match
 
 
 @pytest.fixture(scope="module")
@@ -106,18 +105,7 @@ def test_z_factor_and_angle_lists_match_the_reference(G):
 
 
 def test_signatures_match_the_reference():
-    import neilpy_amd
-    with open(os.path.join(GOLDEN, "surface_signatures.json")) as f:
-        want = json.load(f)
-    assert len(want) == 11
-    for name, params in want.items():
-        got = list(inspect.signature(getattr(neilpy_amd, name)).parameters.values())
-        assert len(got) >= len(params), name
-        for g, p in zip(got, params):
-            assert (g.name, g.kind.name) == (p["name"], p["kind"]), (name, g, p)
-            assert (None if g.default is inspect.Parameter.empty else repr(g.default)) == p["default"], (name, g, p)
-        for g in got[len(params):]:
-            assert g.kind is inspect.Parameter.KEYWORD_ONLY, (name, g)
+    signatures_match("surface_signatures.json", 11)
 
 
 def test_abi_names_exported():
@@ -207,18 +195,9 @@ def test_esri_slope_squares_by_a_product(G):
 def test_surface_kernels_compile_without_scratch(tmp_path):
     """every instance of csrc/surface.hip keeps its state in registers (ScratchSize 0), and the fp32 divides and square
     roots are the correctly rounded sequences (no GPU needed)"""
-    from neilpy_amd.build import CSRC, FLAGS, hipcc
-    out = str(tmp_path / "surface.s")
-    cmd = [hipcc()] + [f for f in FLAGS if f != "-fPIC"] + ["--offload-device-only", "-S",
-                                                           os.path.join(CSRC, "surface.hip"), "-o", out]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    text = open(out).read()
-    kernels = dict(re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", text, re.S))
+    text, kernels = device_asm("surface", tmp_path)
     assert len(kernels) == 18                 # 2 dtypes x 9 modes
-    for name, body in kernels.items():
-        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)) == 0, name
-    assert set(re.findall(r"ScratchSize:\s*(\d+)", text)) == {"0"}
+    assert_no_scratch(text, kernels)
     # laplace in fp32 (Li4) is arithmetic only: its five divides are the div_scale / div_fmas / div_fixup sequence
     parts = re.split(r"\n\s*\.type\s+(_ZN4smrf14surface_kernel\S+),@function\n", text)
     bodies = {parts[i]: parts[i + 1].split(".Lfunc_end")[0] for i in range(1, len(parts), 2)}

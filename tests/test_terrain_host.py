@@ -1,17 +1,16 @@
 """Terrain functions without a GPU: the NumPy restatement of the contract against the reference's goldens, the host
 helpers and tables, signatures, ABI exports, the no-fallback rule and the generated code of csrc/terrain.hip."""
 import ctypes
-import inspect
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import terrain_numpy as tn
-from conftest import GOLDEN, ROOT, golden
+from conftest import ROOT, golden
+from family_checks import assert_no_scratch, device_asm, signatures_match
 
 
 @pytest.fixture(scope="module")
@@ -91,18 +90,7 @@ def test_march_tables():
 
 
 def test_signatures_match_the_reference():
-    import neilpy_amd
-    with open(os.path.join(GOLDEN, "terrain_signatures.json")) as f:
-        want = json.load(f)
-    assert len(want) == 10
-    for name, params in want.items():
-        got = list(inspect.signature(getattr(neilpy_amd, name)).parameters.values())
-        assert len(got) >= len(params), name
-        for g, p in zip(got, params):
-            assert (g.name, g.kind.name) == (p["name"], p["kind"]), (name, g, p)
-            assert (None if g.default is inspect.Parameter.empty else repr(g.default)) == p["default"], (name, g, p)
-        for g in got[len(params):]:
-            assert g.kind is inspect.Parameter.KEYWORD_ONLY, (name, g)
+    signatures_match("terrain_signatures.json", 10)
 
 
 def test_abi_names_exported():
@@ -140,15 +128,6 @@ def test_neighbors_are_validated():
 
 def test_terrain_kernels_compile_without_scratch(tmp_path):
     """every instance of csrc/terrain.hip keeps its state in registers: ScratchSize 0 (no GPU needed)"""
-    from neilpy_amd.build import CSRC, FLAGS, hipcc
-    out = str(tmp_path / "terrain.s")
-    cmd = [hipcc()] + [f for f in FLAGS if f != "-fPIC"] + ["--offload-device-only", "-S",
-                                                           os.path.join(CSRC, "terrain.hip"), "-o", out]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    text = open(out).read()
-    kernels = dict(re.findall(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", text, re.S))
+    text, kernels = device_asm("terrain", tmp_path)
     assert len(kernels) == 16                 # 2 dtypes x 4 modes x {tiled, direct}
-    for name, body in kernels.items():
-        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)) == 0, name
-    assert re.findall(r"ScratchSize:\s*(\d+)", text) and set(re.findall(r"ScratchSize:\s*(\d+)", text)) == {"0"}
+    assert_no_scratch(text, kernels)
