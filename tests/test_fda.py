@@ -118,7 +118,8 @@ def test_hip_vs_oracle_random_holes(gpu_device):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape,frac,seed", [((9, 7), .3, 1), ((40, 33), .5, 2), ((64, 300), .2, 3), ((2, 12), .4, 4),
-                                             ((31, 2), .4, 5), ((120, 90), .85, 6)])
+                                             ((31, 2), .4, 5), ((120, 90), .85, 6), ((2100, 33), .3, 7),
+                                             ((240, 2049), .2, 8)])
 def test_hip_operator_equals_explicit_system(gpu_device, shape, frac, seed):
     """The device A v, A^T u, right-hand side and row multiplicity against the reference's explicit sparse
     system (oracle.fda_system, neilpy.py:1180-1209): a wrong-by-one-equation stencil cannot hide inside the
@@ -183,7 +184,8 @@ def _fixed_reference(shape, frac, seed, K):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("K", (5, 6))
-@pytest.mark.parametrize("shape,frac,seed", [((9, 7), .3, 1), ((40, 33), .5, 2), ((64, 300), .2, 3)])
+@pytest.mark.parametrize("shape,frac,seed", [((9, 7), .3, 1), ((40, 33), .5, 2), ((64, 300), .2, 3), ((2100, 33), .3, 7),
+                                             ((240, 2049), .2, 8)])
 def test_hip_pending_x_at_fixed_iteration(gpu_device, shape, frac, seed, K):
     """The x step left pending at an odd stop: x is written every second iteration, so a solve cut at an odd K owes
     t1_K w_{K-1} in the scatter, and one cut at an even K owes nothing.  The solver is stopped after exactly K iterations
