@@ -3,15 +3,16 @@
 // Measured on MI355X, 16384^2, windows 1..50, this build with SMRF_ERO_INC=2 against the build before it with SMRF_ERO_INC=0
 // (every window on the ring erosion), both interleaved in one process:
 //     SMRF_ERO_INC=2 python tools/window_ab.py --libs parent.so --libs-env SMRF_ERO_INC=0 --windows 50 --reps 5
-// (profiles/incero_overlap.md section 3, profiles/incero_overlap_logs/window_ring_ab.log).  A radius is taken where its whole
-// window is at least 3 percent faster - 17 of the 35 radii 16..50.  The pass costs 0.46 ms with an empty P_R, 0.63-0.66 ms (its
-// three plane touches) with 8 cells and up to 0.86 ms at 48 cells; it wins 4-21 percent of the window at 21, 28, 29, 31, 36, 38
-// and every radius from 40 up.  33, 34, 35 and 39 are 2.2-2.9 percent faster, short of the rule, 32 (32 cells against a fast
-// ring erosion) loses 3 percent, and below R = 28 the ring erosion itself runs at the three-plane-touch time (only R = 21,
-// empty P_R, wins).  R = 51..64 are not measured (the benchmark stops at 50) and stay on the ring erosion.
+// (profiles/incero_mirror.md section 3, profiles/incero_mirror_logs/window_ring_ab.log).  A radius is taken where its whole
+// window is at least 3 percent faster - 23 of the 35 radii 16..50: 21, 28, 29 and every radius from 31 up.  With the mirror
+// plan and a third wave per SIMD the pass costs 0.62-0.67 ms (its three plane touches) up to 36 cells and at most 0.71 ms
+// at 48, so 32, 33, 34, 35, 37 and 39 now win 5-12 percent of the window (they were 2.2-2.9 percent short, 32 lost).  24 and 30
+// met the rule in this measurement (-3.2 and -4.7 percent) but not in the one of an earlier session with the same kernels
+// (-1.5 and -2.2) and stay on the ring erosion; below R = 28 the ring erosion itself runs at the three-plane-touch time (only
+// R = 21, empty P_R, wins).  R = 51..64 are not measured (the benchmark stops at 50) and stay on the ring erosion.
 // (Included inside namespace smrf.)
 inline constexpr unsigned char kEroIncAdoptF32[65] = {
     0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
-    0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 1, 1, 0, 1, 0, 0,
-    0, 0, 1, 0, 1, 0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1,
+    0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 1, 1, 0, 1, 1, 1,
+    1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1,
     0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
