@@ -553,6 +553,45 @@ SMRF_API int smrf_points_nn_search_f64(const double* d_query, int64_t nquery, co
 SMRF_API int smrf_points_nn_sum_f64(const double* d_x, int64_t n, double* d_sum, void* d_workspace,
                      size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * point cloud -> boolean voxel model (neilpy_amd/voxel.py)
+ * ------------------------------------------------------------------------------------------ */
+/* The cloud is three contiguous coordinate arrays of one dtype, 1 <= npoints <= 2^31 - 1.  The volume has nx x ny x nz
+ * cells (any of them may be 0), C order, z fastest. */
+/* Bytes of device scratch the bounds reduction needs. */
+#define SMRF_VOXEL_BOUNDS_BYTES 57344
+/* One reduction over the three arrays: h_box = (min_x, max_x, min_y, max_y, min_z, max_z) as float64 (a NaN is skipped,
+ * an infinity is not), h_nonfinite = the number of coordinates that are NaN or infinite.  Per-workgroup partials, finished
+ * on the host: no float atomics.  Synchronises the stream. */
+SMRF_API int smrf_voxel_bounds_f32(const float* d_x, const float* d_y, const float* d_z, int64_t npoints, double* h_box,
+                     int64_t* h_nonfinite, void* d_workspace, size_t workspace_bytes, void* stream);
+SMRF_API int smrf_voxel_bounds_f64(const double* d_x, const double* d_y, const double* d_z, int64_t npoints,
+                     double* h_box, int64_t* h_nonfinite, void* d_workspace, size_t workspace_bytes, void* stream);
+/* Workspace of mark and expand, 0 for a volume out of range (a negative extent, threshold < 1, more than 2^31 - 1 columns
+ * or 2^40 entries).
+ * It begins with the marks: for threshold == 1 a bit set, uint32 words [nx][ny][ceil(nz / 32)], bit (z & 31) of word
+ * z >> 5 for cell z, 1/8 B per voxel; for threshold > 1 uint32 counts [nx][ny][nz], 4 B per voxel.  The lowest occupied
+ * cell of every column (int32 [nx][ny]) follows at the next multiple of 256 bytes. */
+SMRF_API size_t smrf_voxel_workspace_bytes(int nx, int ny, int nz, int threshold);
+/* Clears the marks, then bins every point: d = v - h_offsets[axis], one subtraction rounded in the cloud's dtype
+ * (h_offsets holds three values of that dtype, widened); its bin on an axis with edges e[0..nb] (float64, device,
+ * non-decreasing, nb + 1 of them, used as handed in) is numpy.histogramdd's: searchsorted(e, d, side='right') - 1 compared
+ * in float64, d == e[nb] in bin nb - 1, and the point is dropped when d < e[0] or d > e[nb] on any axis.  threshold == 1
+ * sets the cell's bit (the word is read first and the atomic OR issued only for a clear bit); threshold > 1 adds 1 to the
+ * cell's count with an integer atomic.  Either way the marks are a function of the input alone. */
+SMRF_API int smrf_voxel_mark_f32(const float* d_x, const float* d_y, const float* d_z, int64_t npoints,
+                     const double* h_offsets, const double* d_xedges, const double* d_yedges, const double* d_zedges,
+                     int nx, int ny, int nz, int threshold, void* d_workspace, size_t workspace_bytes, void* stream);
+SMRF_API int smrf_voxel_mark_f64(const double* d_x, const double* d_y, const double* d_z, int64_t npoints,
+                     const double* h_offsets, const double* d_xedges, const double* d_yedges, const double* d_zedges,
+                     int nx, int ny, int nz, int threshold, void* d_workspace, size_t workspace_bytes, void* stream);
+/* From the marks of a workspace (same nx, ny, nz, threshold) to d_out, uint8 0 / 1, [nx][ny][nz + pad], 4-byte aligned:
+ * out[x][y][pad + z] = (bit set, or count >= threshold), or with bottom_fill != 0 also z below the lowest such cell of a
+ * column that has one; out[x][y][0..pad) = 1 for every column.  nx * ny * (nz + pad) <= 2^42.  Writes the column minima
+ * into the workspace on the way. */
+SMRF_API int smrf_voxel_expand(void* d_workspace, size_t workspace_bytes, int nx, int ny, int nz, int threshold,
+                     int bottom_fill, int pad, uint8_t* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,9 @@ infill, and ``nearest_source`` the distance / index planes behind it (neilpy_amd
 rest on it (neilpy_amd/focal.py).  ``scaled_morphometry`` / ``vip_score`` / ``ashift`` are the multi-scale tools, strided
 stencils under ashift's edge rule, with the host helper ``triangle_height`` (neilpy_amd/morphometry.py).
 ``chamfer_distance`` compares two point clouds and ``nearest_points`` is the exact nearest-neighbour query under it, a
-counting sort into a cell grid and a ring search (neilpy_amd/points.py).
+counting sort into a cell grid and a ring search (neilpy_amd/points.py).  ``voxelize`` turns a cloud into the boolean
+voxel model ``np.histogramdd`` and a threshold give, bit for bit: a scatter into a bit set and a byte expansion with the
+bottom fill (neilpy_amd/voxel.py).
 """
 from ._lib import SmrfHipError, load as load_library, LIB_PATH          # noqa: F401
 from .affine import Affine, edges_from_IT, from_origin, write_worldfile                 # noqa: F401
@@ -27,6 +29,7 @@ from .surface import (aspect, curvature, esri_curvature, esri_slope, evans_curva
                       multiple_illumination, slope, wilson_gallant_curvature, z_factor,
                       zevenbergen_and_thorne_curvature)
 from .synth import synth_dem, synth_points                               # noqa: F401
+from .voxel import voxelize                                                # noqa: F401
 from .terrain import (count_openness, geomorphon_cmap, geomorphons, get_lowest_equivalent, int2base,   # noqa: F401
                       openness, progressive_window, skyview_factor, ternary_pattern_from_openness,
                       terrain_code_to_geomorphon)

@@ -116,6 +116,12 @@ SIGNATURES = {
     "smrf_points_nn_build_f64": (_i, [_p, _i64, _i, C.POINTER(_d), _p, _sz, _p]),
     "smrf_points_nn_search_f64": (_i, [_p, _i64, _p, _i64, _i, C.POINTER(_d), _p, _p, _p, _sz, _p]),
     "smrf_points_nn_sum_f64": (_i, [_p, _i64, _p, _p, _sz, _p]),
+    "smrf_voxel_bounds_f32": (_i, [_p, _p, _p, _i64, C.POINTER(_d), C.POINTER(_i64), _p, _sz, _p]),
+    "smrf_voxel_bounds_f64": (_i, [_p, _p, _p, _i64, C.POINTER(_d), C.POINTER(_i64), _p, _sz, _p]),
+    "smrf_voxel_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "smrf_voxel_mark_f32": (_i, [_p, _p, _p, _i64, C.POINTER(_d), _p, _p, _p, _i, _i, _i, _i, _p, _sz, _p]),
+    "smrf_voxel_mark_f64": (_i, [_p, _p, _p, _i64, C.POINTER(_d), _p, _p, _p, _i, _i, _i, _i, _p, _sz, _p]),
+    "smrf_voxel_expand": (_i, [_p, _sz, _i, _i, _i, _i, _i, _i, _p, _p]),
 }
 
 _lib = None
