@@ -14,7 +14,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _cloud, _lib
 from ._device import device_scoped as _device_scoped, is_tensor as _is_tensor
 from ._raster import Raster, _ptr, _stream, _suffix, _to_device, _torch
 from ._xfer import to_host as _d2h
@@ -151,15 +151,9 @@ def progressive_filter(Z, windows, cellsize=1, slope_threshold=.15, return_when_
 # ------------------------------------------------------------------------------------------
 def _dem_edges(xd, yd, cellsize):
     """Cell edges of create_dem's raster from the points' extent (neilpy.py:1117-1124)."""
-    torch = _torch()
-    lib = _lib.load()
-    npts = xd.numel()
-    if npts == 0:
+    if xd.numel() == 0:
         raise ValueError("zero-size array to reduction operation minimum which has no identity")
-    ws = torch.empty(4 * 1024, dtype=torch.float64, device=xd.device)
-    ext = (C.c_double * 4)()
-    _lib.check(lib.smrf_points_extent_f64(_ptr(xd), _ptr(yd), npts, ext, _ptr(ws), ws.numel() * 8, _stream()))
-    return _edges_from_extent(*(np.float64(v) for v in ext), cellsize)
+    return _edges_from_extent(*(np.float64(v) for v in _cloud.extent(xd, yd)), cellsize)
 
 
 def _edges_from_extent(xmin, xmax, ymin, ymax, cellsize):
@@ -173,37 +167,26 @@ def _edges_from_extent(xmin, xmax, ymin, ymax, cellsize):
 
 def _create_dem_device(xd, yd, zd, cellsize, bin_type, edges):
     """Device core: returns (float64 grid CUDA tensor, uint8 empty mask CUDA tensor, transform)."""
-    torch = _torch()
-    lib = _lib.load()
-    npts = xd.numel()
     h_filter = None
     if edges is None:
         xedges, yedges = _dem_edges(xd, yd, cellsize)
     else:
         xedges, yedges = edges[0], edges[1]
-        h_filter = (C.c_double * 4)(float(xedges[0]), float(xedges[-1]), float(yedges[-1]), float(yedges[0]))
+        h_filter = (xedges[0], xedges[-1], yedges[-1], yedges[0])
         cellsize = np.abs(xedges[1] - xedges[0])
     nx, ny = len(xedges) - 1, len(yedges) - 1
     t = from_origin(xedges[0], yedges[0], cellsize, cellsize)
-    inv = ~t
-    h_inv = (C.c_double * 6)(*[float(v) for v in tuple(inv)[:6]])
-    is_max = 1 if bin_type == 'max' else 0
-    keys = torch.empty((max(ny, 0), max(nx, 0)), dtype=torch.int64, device=xd.device)
-    n_out = torch.zeros(1, dtype=torch.int64, device=xd.device)
-    grid = torch.empty((max(ny, 0), max(nx, 0)), dtype=torch.float64, device=xd.device)
-    empty = torch.empty((max(ny, 0), max(nx, 0)), dtype=torch.uint8, device=xd.device)
     if nx < 1 or ny < 1:
-        if npts:
+        if xd.numel():
             raise ValueError("invalid entry in coordinates array")
-        return grid, empty, t
-    _lib.check(lib.smrf_grid_clear_u64(_ptr(keys), keys.numel(), _stream()))
-    _lib.check(lib.smrf_grid_bin_f64(_ptr(xd), _ptr(yd), _ptr(zd), npts, h_inv, h_filter, _ptr(keys), ny, nx, 0, ny,
-                                     is_max, _ptr(n_out), _stream()))
-    if int(n_out.item()) > 0:
+        torch = _torch()
+        return (torch.empty((max(ny, 0), max(nx, 0)), dtype=torch.float64, device=xd.device),
+                torch.empty((max(ny, 0), max(nx, 0)), dtype=torch.uint8, device=xd.device), t)
+    grid, empty, n_out = _cloud.grid_rows(xd, yd, zd, tuple(~t)[:6], (ny, nx), 0, ny, bin_type, h_filter)
+    if n_out > 0:
         raise ValueError("invalid entry in coordinates array")       # np.ravel_multi_index, neilpy.py:1151
     if bin_type not in ('max', 'min'):
         raise ValueError('This type not supported.')                  # neilpy.py:1158
-    _lib.check(lib.smrf_grid_finalize_f64(_ptr(keys), _ptr(grid), _ptr(empty), keys.numel(), is_max, _stream()))
     return grid, empty, t
 
 

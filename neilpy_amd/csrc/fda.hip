@@ -199,8 +199,8 @@ struct FdaLayout { size_t plane, bytes, x, v, w, u, hole, cnt, part, red, sc, to
 FdaLayout fda_layout(int rows, int cols) {
   FdaLayout L;
   const size_t n = (size_t)rows * (size_t)cols;
-  L.plane = align_up(n * sizeof(double));
-  L.bytes = align_up(n);
+  L.plane = smrf_up256(n * sizeof(double));
+  L.bytes = smrf_up256(n);
   size_t o = 0;
   L.x = o; o += L.plane;
   L.v = o; o += L.plane;
@@ -208,9 +208,9 @@ FdaLayout fda_layout(int rows, int cols) {
   L.u = o; o += L.plane;
   L.hole = o; o += L.bytes;
   L.cnt = o; o += L.bytes;
-  L.part = o; o += align_up(2 * MAXB * sizeof(double));
+  L.part = o; o += smrf_up256(2 * MAXB * sizeof(double));
   L.red = o; o += 256;
-  L.sc = o; o += align_up(sizeof(Sc));
+  L.sc = o; o += smrf_up256(sizeof(Sc));
   L.total = o;
   return L;
 }
@@ -226,7 +226,7 @@ Fda fda_bind(void* ws, int rows, int cols) {
 }
 // 1-D launch of the mask and scatter kernels
 int fda_grid1d(int rows, int cols) {
-  return (int)std::max<long long>(1, std::min<long long>(((long long)rows * cols + 255) / 256, MAXB));
+  return smrf_blocks((long long)rows * cols, MAXB);
 }
 
 }  // namespace

@@ -6,9 +6,7 @@
 // the float64 bit pattern made monotone (sign flip), so unsigned 64-bit atomicMin implements an
 // exact floating-point min (and, on the complemented key, max) including +-inf; all-ones marks an
 // empty cell, which no non-NaN value maps to.  HBM-bound: 24 B read per point + one 8 B atomic.
-#include <algorithm>
-
-#include "smrf_common.h"
+#include "cloud_reduce.h"
 
 namespace {
 
@@ -21,35 +19,12 @@ __device__ __forceinline__ double key_f64(unsigned long long k) {
   return __longlong_as_double((long long)k);
 }
 
-__global__ __launch_bounds__(256) void extent_kernel(const double* __restrict__ x, const double* __restrict__ y,
-                                                     long long n, double* __restrict__ part) {
-  double xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
-  bool bad = false;
-  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const double a = x[i], b = y[i];
-    bad |= (a != a) | (b != b);
-    xmin = fmin(xmin, a); xmax = fmax(xmax, a);
-    ymin = fmin(ymin, b); ymax = fmax(ymax, b);
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    xmin = fmin(xmin, __shfl_down(xmin, o, 64)); xmax = fmax(xmax, __shfl_down(xmax, o, 64));
-    ymin = fmin(ymin, __shfl_down(ymin, o, 64)); ymax = fmax(ymax, __shfl_down(ymax, o, 64));
-    bad |= (bool)__shfl_down((int)bad, o, 64);
-  }
-  __shared__ double s[4][4];
-  __shared__ int sbad[4];
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { s[0][w] = xmin; s[1][w] = xmax; s[2][w] = ymin; s[3][w] = ymax; sbad[w] = bad; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const bool b = sbad[0] | sbad[1] | sbad[2] | sbad[3];
-    // np.min / np.max propagate NaN (neilpy.py:1121-1124 would then build a NaN-sized grid)
-    part[blockIdx.x * 4 + 0] = b ? NAN : fmin(fmin(s[0][0], s[0][1]), fmin(s[0][2], s[0][3]));
-    part[blockIdx.x * 4 + 1] = b ? NAN : fmax(fmax(s[1][0], s[1][1]), fmax(s[1][2], s[1][3]));
-    part[blockIdx.x * 4 + 2] = b ? NAN : fmin(fmin(s[2][0], s[2][1]), fmin(s[2][2], s[2][3]));
-    part[blockIdx.x * 4 + 3] = b ? NAN : fmax(fmax(s[3][0], s[3][1]), fmax(s[3][2], s[3][3]));
-  }
-}
+// create_dem's separate x and y arrays; np.min / np.max propagate NaN (neilpy.py:1121-1124 would then build a NaN-sized
+// grid), so the extent is cloud_reduce.h's CLOUD_POISON
+struct XyLoad {
+  const double *x, *y;
+  __device__ void operator()(long long i, double* v) const { v[0] = x[i]; v[1] = y[i]; }
+};
 
 __global__ __launch_bounds__(256) void fill_u64_kernel(unsigned long long* __restrict__ p, long long n) {
   for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) p[i] = ~0ull;
@@ -198,8 +173,6 @@ __global__ __launch_bounds__(256) void band_pack_kernel(const BucketArgs a, unsi
   }
 }
 
-int nblocks(long long n, int cap) { return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, cap)); }
-
 }  // namespace
 
 extern "C" {
@@ -208,31 +181,16 @@ int smrf_points_extent_f64(const double* d_x, const double* d_y, int64_t n, doub
                            size_t workspace_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!d_x || !d_y || !h_out || n < 1) return smrf_fail(SMRF_E_ARG, "extent needs at least one point");
-  const int blocks = nblocks(n, 1024);
-  if (!d_workspace || workspace_bytes < (size_t)blocks * 4 * sizeof(double))
-    return smrf_fail(SMRF_E_WORKSPACE, "extent workspace too small");
-  double* part = (double*)d_workspace;
-  hipLaunchKernelGGL(extent_kernel, dim3(blocks), dim3(256), 0, stream, d_x, d_y, (long long)n, part);
-  SMRF_LAUNCH_CHECK();
-  static thread_local double host[4 * 1024];
-  SMRF_HIP_CHECK(hipMemcpyAsync(host, part, (size_t)blocks * 4 * sizeof(double), hipMemcpyDeviceToHost, stream));
-  SMRF_HIP_CHECK(hipStreamSynchronize(stream));
-  double r[4] = {INFINITY, -INFINITY, INFINITY, -INFINITY};
-  bool bad = false;
-  for (int b = 0; b < blocks; ++b) {
-    for (int k = 0; k < 4; ++k) bad |= (host[b * 4 + k] != host[b * 4 + k]);
-    r[0] = std::min(r[0], host[b * 4 + 0]); r[1] = std::max(r[1], host[b * 4 + 1]);
-    r[2] = std::min(r[2], host[b * 4 + 2]); r[3] = std::max(r[3], host[b * 4 + 3]);
-  }
-  for (int k = 0; k < 4; ++k) h_out[k] = bad ? NAN : r[k];
-  return SMRF_OK;
+  using namespace smrf;
+  return cloud_bounds<2, 2, CLOUD_POISON>(XyLoad{d_x, d_y}, n, h_out, nullptr, d_workspace, workspace_bytes,
+                                          cloud_bytes(2, CLOUD_POISON, smrf_blocks(n, CLOUD_PARTS)), stream);
 }
 
 int smrf_affine_apply_f64(const double* d_x, const double* d_y, int64_t npts, const double* h_inv, double* d_col,
                           double* d_row, void* stream) {
   if (npts < 0 || !h_inv || (npts > 0 && (!d_x || !d_y || !d_col || !d_row))) return smrf_fail(SMRF_E_ARG, "null pointer");
   if (npts == 0) return SMRF_OK;
-  hipLaunchKernelGGL(affine_kernel, dim3(nblocks(npts, 8192)), dim3(256), 0, (hipStream_t)stream, d_x, d_y,
+  hipLaunchKernelGGL(affine_kernel, dim3(smrf_blocks(npts, 8192)), dim3(256), 0, (hipStream_t)stream, d_x, d_y,
                      (long long)npts, h_inv[0], h_inv[1], h_inv[2], h_inv[3], h_inv[4], h_inv[5], d_col, d_row);
   SMRF_LAUNCH_CHECK();
   return SMRF_OK;
@@ -243,7 +201,7 @@ int smrf_las_decode_xyz_f64(const uint8_t* d_records, int64_t npts, int record_l
   if (npts < 0 || record_length < 12 || !h_scale_offset || (npts > 0 && (!d_records || !d_x || !d_y || !d_z)))
     return smrf_fail(SMRF_E_ARG, "bad LAS decode arguments");
   if (npts == 0) return SMRF_OK;
-  hipLaunchKernelGGL(las_decode_kernel, dim3(nblocks(npts, 8192)), dim3(256), 0, (hipStream_t)stream, d_records,
+  hipLaunchKernelGGL(las_decode_kernel, dim3(smrf_blocks(npts, 8192)), dim3(256), 0, (hipStream_t)stream, d_records,
                      (long long)npts, record_length, h_scale_offset[0], h_scale_offset[1], h_scale_offset[2],
                      h_scale_offset[3], h_scale_offset[4], h_scale_offset[5], d_x, d_y, d_z);
   SMRF_LAUNCH_CHECK();
@@ -268,7 +226,7 @@ int smrf_points_band_count_f64(const double* d_x, const double* d_y, int64_t npt
   if (!d_counts) return smrf_fail(SMRF_E_ARG, "null pointer");
   SMRF_HIP_CHECK(hipMemsetAsync(d_counts, 0, (size_t)nbands * sizeof(uint64_t), (hipStream_t)stream));
   if (npts == 0) return SMRF_OK;
-  hipLaunchKernelGGL(band_count_kernel, dim3(nblocks((npts + 15) / 16, 4096)), dim3(256), 0, (hipStream_t)stream, a,
+  hipLaunchKernelGGL(band_count_kernel, dim3(smrf_blocks((npts + 15) / 16, 4096)), dim3(256), 0, (hipStream_t)stream, a,
                      (unsigned long long*)d_counts);
   SMRF_LAUNCH_CHECK();
   return SMRF_OK;
@@ -281,7 +239,7 @@ int smrf_points_band_pack_f64(const double* d_x, const double* d_y, const double
   if (int rc = bucket_args(a, d_x, d_y, d_z, npts, h_inv, rows_total, nbands)) return rc;
   if (npts == 0) return SMRF_OK;
   if (!d_z || !d_cursors || !d_out_x || !d_out_y || !d_out_z) return smrf_fail(SMRF_E_ARG, "null pointer");
-  hipLaunchKernelGGL(band_pack_kernel, dim3(nblocks((npts + 15) / 16, 4096)), dim3(256), 0, (hipStream_t)stream, a,
+  hipLaunchKernelGGL(band_pack_kernel, dim3(smrf_blocks((npts + 15) / 16, 4096)), dim3(256), 0, (hipStream_t)stream, a,
                      (unsigned long long*)d_cursors, d_out_x, d_out_y, d_out_z);
   SMRF_LAUNCH_CHECK();
   return SMRF_OK;
@@ -290,7 +248,7 @@ int smrf_points_band_pack_f64(const double* d_x, const double* d_y, const double
 int smrf_grid_clear_u64(uint64_t* d_keys, int64_t ncells, void* stream) {
   if (!d_keys || ncells < 0) return smrf_fail(SMRF_E_ARG, "bad grid");
   if (ncells == 0) return SMRF_OK;
-  hipLaunchKernelGGL(fill_u64_kernel, dim3(nblocks(ncells, 8192)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(fill_u64_kernel, dim3(smrf_blocks(ncells, 8192)), dim3(256), 0, (hipStream_t)stream,
                      (unsigned long long*)d_keys, (long long)ncells);
   SMRF_LAUNCH_CHECK();
   return SMRF_OK;
@@ -313,7 +271,7 @@ int smrf_grid_bin_f64(const double* d_x, const double* d_y, const double* d_z, i
   a.keys = (unsigned long long*)d_keys;
   a.rows_total = rows_total; a.cols = cols; a.row0 = row0; a.rows_local = rows_local; a.is_max = is_max != 0;
   a.n_outside = (unsigned long long*)d_n_outside;
-  hipLaunchKernelGGL(bin_kernel, dim3(nblocks(npts, 8192)), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(bin_kernel, dim3(smrf_blocks(npts, 8192)), dim3(256), 0, (hipStream_t)stream, a);
   SMRF_LAUNCH_CHECK();
   return SMRF_OK;
 }
@@ -322,7 +280,7 @@ int smrf_grid_finalize_f64(const uint64_t* d_keys, double* d_grid, uint8_t* d_em
                            void* stream) {
   if (!d_keys || !d_grid || ncells < 0) return smrf_fail(SMRF_E_ARG, "bad grid");
   if (ncells == 0) return SMRF_OK;
-  hipLaunchKernelGGL(finalize_kernel, dim3(nblocks(ncells, 8192)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(finalize_kernel, dim3(smrf_blocks(ncells, 8192)), dim3(256), 0, (hipStream_t)stream,
                      (const unsigned long long*)d_keys, d_grid, d_empty, (long long)ncells, is_max != 0);
   SMRF_LAUNCH_CHECK();
   return SMRF_OK;

@@ -18,8 +18,6 @@ namespace {
 #endif
 constexpr int MAXB = SMRF_LSQR_MAXB;   // most blocks per vector kernel = partial sums per reduction
 
-inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // 2-D launch of the stencil kernels: 256 columns per block, rows strided over gridDim.y; at most MAXB blocks
 inline dim3 lsqr_grid2d(int rows, int cols) {
   const int cb = (cols + 255) / 256;

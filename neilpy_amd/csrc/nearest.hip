@@ -37,15 +37,13 @@ struct NearestWs {
   int* z;           // [rows][cols]   first column the entry wins from
 };
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 inline size_t nearest_layout(int rows, int cols, char* base, NearestWs* w) {
   const size_t strips = (rows + NSTRIP - 1) / NSTRIP, nseg = (cols + NSEG - 1) / NSEG;
-  const size_t plane = up256(strips * (size_t)cols * 4), cells = (size_t)rows * cols;
+  const size_t plane = smrf_up256(strips * (size_t)cols * 4), cells = (size_t)rows * cols;
   size_t off = 0;
   auto take = [&](size_t bytes) {
     char* p = base + off;
-    off += up256(bytes);
+    off += smrf_up256(bytes);
     return p;
   };
   uint32_t* mask = (uint32_t*)take(plane);

@@ -2,7 +2,7 @@
 // chamfer_distance at neilpy.py:2679 asks a KD-tree): a counting sort of the cloud into a uniform grid of square cells and
 // one search kernel.  DESIGN.md section 14 is the contract.
 //
-//   bounds    points_bounds_kernel: box of the two planar axes and the number of non-finite coordinates, one reduction.
+//   bounds    cloud_reduce.h over RowLoad: box of the two planar axes and the number of non-finite coordinates.
 //   grid      points_grid(): a square cell sized for about two points per cell over the box of axes 0 and 1.  The grid
 //             has two axes whatever the dimension, so a 2.5-D lidar cloud does not make a mostly empty lattice; the third
 //             coordinate only enters the distance.
@@ -33,12 +33,12 @@
 #include <climits>
 #include <cmath>
 
-#include "smrf_common.h"
+#include "cloud_reduce.h"
 
 namespace smrf {
 
 constexpr int PN_SCAN = 2048;        // cell counts per workgroup of the scan: 256 threads x 8
-constexpr int PN_PARTS = 1024;       // workgroups of the bounds and of the sum reduction at most
+constexpr int PN_PARTS = CLOUD_PARTS;   // workgroups of the bounds and of the sum reduction at most
 constexpr long long PN_MAX_POINTS = 1ll << 30;   // rows are int32 and cell indices fit int32
 
 struct PointsGrid {
@@ -88,18 +88,16 @@ struct PointsWs {
   double* sorted;    // [n * dim]   its coordinates
 };
 
-inline size_t pn_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // the same offsets for every call with the same (n, dim): the search finds what the build left
 inline size_t points_layout(long long n, int dim, char* base, PointsWs* w) {
   const size_t cap = (size_t)points_cells_cap(n);
   size_t off = 0;
   auto take = [&](size_t bytes) {
     char* p = base + off;
-    off += pn_up256(bytes);
+    off += smrf_up256(bytes);
     return p;
   };
-  double* part = (double*)take((size_t)PN_PARTS * 5 * sizeof(double));
+  double* part = (double*)take(cloud_bytes(2, CLOUD_COUNT, PN_PARTS));
   unsigned* start = (unsigned*)take((cap + 1) * 4);
   unsigned* cnt = (unsigned*)take(cap * 4);
   unsigned* bsum = (unsigned*)take(((cap + PN_SCAN - 1) / PN_SCAN) * 4);
@@ -110,42 +108,18 @@ inline size_t points_layout(long long n, int dim, char* base, PointsWs* w) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// bounds: box of axes 0 and 1, count of non-finite coordinates over all axes.  (grid.hip's extent_kernel serves
-// create_dem's separate x and y arrays and answers a NaN with a NaN box; here rows of dim doubles are read and the
-// non-finite coordinates counted, inf included, so the caller can refuse the cloud.)
+// bounds: box of axes 0 and 1, count of non-finite coordinates over all axes, inf included, so the caller can refuse
+// the cloud (cloud_reduce.h, CLOUD_COUNT); this is how a row of DIM doubles is read
 // ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void points_bounds_kernel(const double* __restrict__ p, long long n, int dim,
-                                                            double* __restrict__ part) {
-  double xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY;
-  unsigned long long bad = 0;
-  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const double* q = p + i * dim;
-    const double a = q[0], b = q[1];
-    bad += !(fabs(a) < INFINITY);
-    bad += !(fabs(b) < INFINITY);
-    if (dim == 3) bad += !(fabs(q[2]) < INFINITY);
-    xmin = fmin(xmin, a); xmax = fmax(xmax, a);
-    ymin = fmin(ymin, b); ymax = fmax(ymax, b);
+template <int DIM>
+struct RowLoad {
+  const double* p;
+  __device__ void operator()(long long i, double* v) const {
+    const double* q = p + i * DIM;
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) v[a] = q[a];
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    xmin = fmin(xmin, __shfl_down(xmin, o, 64)); xmax = fmax(xmax, __shfl_down(xmax, o, 64));
-    ymin = fmin(ymin, __shfl_down(ymin, o, 64)); ymax = fmax(ymax, __shfl_down(ymax, o, 64));
-    bad += __shfl_down(bad, o, 64);
-  }
-  __shared__ double s[4][4];
-  __shared__ unsigned long long sbad[4];
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { s[0][w] = xmin; s[1][w] = xmax; s[2][w] = ymin; s[3][w] = ymax; sbad[w] = bad; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double* o = part + blockIdx.x * 5;
-    o[0] = fmin(fmin(s[0][0], s[0][1]), fmin(s[0][2], s[0][3]));
-    o[1] = fmax(fmax(s[1][0], s[1][1]), fmax(s[1][2], s[1][3]));
-    o[2] = fmin(fmin(s[2][0], s[2][1]), fmin(s[2][2], s[2][3]));
-    o[3] = fmax(fmax(s[3][0], s[3][1]), fmax(s[3][2], s[3][3]));
-    o[4] = (double)(sbad[0] + sbad[1] + sbad[2] + sbad[3]);   // < 2^53: exact
-  }
-}
+};
 
 // ---------------------------------------------------------------------------------------------------------------
 // counting sort into cell order
@@ -348,8 +322,6 @@ __global__ __launch_bounds__(256) void points_sum_kernel(const double* __restric
   if (threadIdx.x == 0) out[blockIdx.x] = v;
 }
 
-inline int pn_blocks(long long n, int cap) { return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, cap)); }
-
 inline int points_args(long long n, int dim) {
   if (dim < 2 || dim > 3) return smrf_fail(SMRF_E_ARG, "points of dimension %d: 2 or 3 expected", dim);
   if (n < 1 || n > PN_MAX_POINTS) return smrf_fail(SMRF_E_ARG, "%lld points: 1 to %lld expected", n, PN_MAX_POINTS);
@@ -371,25 +343,12 @@ int smrf_points_nn_bounds_f64(const double* d_points, int64_t npoints, int dim, 
   hipStream_t stream = (hipStream_t)stream_;
   if (dim < 2 || dim > 3 || npoints < 1) return smrf_fail(SMRF_E_ARG, "bounds of %lld points of dimension %d", (long long)npoints, dim);
   if (!d_points || !h_box || !h_nonfinite) return smrf_fail(SMRF_E_ARG, "null pointer");
-  if (!d_workspace || workspace_bytes < (size_t)PN_PARTS * 5 * sizeof(double))
-    return smrf_fail(SMRF_E_WORKSPACE, "bounds workspace too small");
-  const int blocks = pn_blocks(npoints, PN_PARTS);
-  double* part = (double*)d_workspace;
-  hipLaunchKernelGGL(points_bounds_kernel, dim3(blocks), dim3(256), 0, stream, d_points, (long long)npoints, dim, part);
-  SMRF_LAUNCH_CHECK();
-  static thread_local double host[PN_PARTS * 5];
-  SMRF_HIP_CHECK(hipMemcpyAsync(host, part, (size_t)blocks * 5 * sizeof(double), hipMemcpyDeviceToHost, stream));
-  SMRF_HIP_CHECK(hipStreamSynchronize(stream));
-  double r[4] = {INFINITY, -INFINITY, INFINITY, -INFINITY};
-  double bad = 0.0;
-  for (int b = 0; b < blocks; ++b) {
-    r[0] = std::min(r[0], host[b * 5 + 0]); r[1] = std::max(r[1], host[b * 5 + 1]);
-    r[2] = std::min(r[2], host[b * 5 + 2]); r[3] = std::max(r[3], host[b * 5 + 3]);
-    bad += host[b * 5 + 4];
-  }
-  for (int k = 0; k < 4; ++k) h_box[k] = r[k];
-  *h_nonfinite = (int64_t)bad;
-  return SMRF_OK;
+  const size_t need = cloud_bytes(2, CLOUD_COUNT, PN_PARTS);
+  if (dim == 2)
+    return cloud_bounds<2, 2, CLOUD_COUNT>(RowLoad<2>{d_points}, npoints, h_box, h_nonfinite, d_workspace, workspace_bytes,
+                                           need, stream);
+  return cloud_bounds<2, 3, CLOUD_COUNT>(RowLoad<3>{d_points}, npoints, h_box, h_nonfinite, d_workspace, workspace_bytes,
+                                         need, stream);
 }
 
 int smrf_points_nn_build_f64(const double* d_points, int64_t npoints, int dim, const double* h_box, void* d_workspace,
@@ -407,7 +366,7 @@ int smrf_points_nn_build_f64(const double* d_points, int64_t npoints, int dim, c
   points_layout(npoints, dim, (char*)d_workspace, &w);
   const PointsGrid g = points_grid(h_box, npoints);
   const long long cells = (long long)g.nx * g.ny, nb = (cells + PN_SCAN - 1) / PN_SCAN;
-  const int blocks = pn_blocks(npoints, 8192);
+  const int blocks = smrf_blocks(npoints, 8192);
   SMRF_HIP_CHECK(hipMemsetAsync(w.cnt, 0, (size_t)cells * 4, stream));
   hipLaunchKernelGGL(points_count_kernel, dim3(blocks), dim3(256), 0, stream, d_points, (long long)npoints, dim, g, w.cnt);
   SMRF_LAUNCH_CHECK();
@@ -456,7 +415,7 @@ int smrf_points_nn_sum_f64(const double* d_x, int64_t n, double* d_sum, void* d_
   if (n < 1 || !d_x || !d_sum) return smrf_fail(SMRF_E_ARG, "sum of %lld values", (long long)n);
   if (!d_workspace || workspace_bytes < (size_t)PN_PARTS * sizeof(double))
     return smrf_fail(SMRF_E_WORKSPACE, "sum workspace too small");
-  const int blocks = pn_blocks(n, PN_PARTS);
+  const int blocks = smrf_blocks(n, PN_PARTS);
   double* part = (double*)d_workspace;
   hipLaunchKernelGGL(points_sum_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_x, (long long)n, part);
   SMRF_LAUNCH_CHECK();

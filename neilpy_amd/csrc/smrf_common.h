@@ -81,6 +81,12 @@ struct SmrfSwitches {
 };
 SMRF_HIDDEN const SmrfSwitches& smrf_sw();
 
+// workgroups of 256 threads of a grid-stride loop over n items: one per 256 items, at least 1 and at most cap
+inline int smrf_blocks(long long n, int cap) { return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, cap)); }
+
+// a byte count rounded up to the 256-byte granule every part of a workspace starts on
+inline size_t smrf_up256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
 // integer floor(sqrt(v)), v >= 0
 __host__ __device__ constexpr int smrf_isqrt(int v) {
   int r = 0;

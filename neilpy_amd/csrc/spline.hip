@@ -255,8 +255,6 @@ __global__ __launch_bounds__(256) void classify_kernel(const double* __restrict_
   }
 }
 
-int grid_for(long long n) { return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 8192)); }
-
 }  // namespace
 
 extern "C" {
@@ -299,7 +297,7 @@ int smrf_spline_eval_f64(const double* d_C, int rows, int cols, const double* d_
   if (rows < 4 || cols < 4) return smrf_fail(SMRF_E_ARG, "a bicubic spline needs at least 4 x 4 cells");
   if (npts == 0) return SMRF_OK;
   EvalArgs a{d_C, rows, cols, d_tx, d_ty, d_px, d_py, (long long)npts, d_out};
-  hipLaunchKernelGGL(eval_kernel, dim3(grid_for(npts)), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(eval_kernel, dim3(smrf_blocks(npts, 8192)), dim3(256), 0, (hipStream_t)stream, a);
   SMRF_LAUNCH_CHECK();
   return SMRF_OK;
 }
@@ -308,7 +306,7 @@ int smrf_classify_points_f64(const double* d_elev, const double* d_slope, const 
                              double elevation_threshold, double elevation_scaler, uint8_t* d_is_object, void* stream) {
   if (npts < 0 || (npts > 0 && (!d_elev || !d_slope || !d_z || !d_is_object))) return smrf_fail(SMRF_E_ARG, "null pointer");
   if (npts == 0) return SMRF_OK;
-  hipLaunchKernelGGL(classify_kernel, dim3(grid_for(npts)), dim3(256), 0, (hipStream_t)stream, d_elev, d_slope, d_z,
+  hipLaunchKernelGGL(classify_kernel, dim3(smrf_blocks(npts, 8192)), dim3(256), 0, (hipStream_t)stream, d_elev, d_slope, d_z,
                      (long long)npts, elevation_threshold, elevation_scaler, d_is_object);
   SMRF_LAUNCH_CHECK();
   return SMRF_OK;

@@ -318,18 +318,18 @@ long long padded_pitch(int cols) {
 Layout layout_of(int rows, int cols, long long ld) {
   Layout L;
   const size_t n2 = (size_t)(rows + 2) * (size_t)ld;
-  L.plane = align_up(n2 * sizeof(double));
+  L.plane = smrf_up256(n2 * sizeof(double));
   size_t o = 0;
   L.x = o; o += L.plane;
   L.v = o; o += L.plane;
   L.w = o; o += L.plane;
   L.uh = o; o += L.plane;
   L.uv = o; o += L.plane;
-  L.hole = o; o += align_up(n2);
-  L.abelow = o; o += align_up((size_t)cols * sizeof(double));
-  L.part = o; o += align_up(2 * MAXB * sizeof(double));
+  L.hole = o; o += smrf_up256(n2);
+  L.abelow = o; o += smrf_up256((size_t)cols * sizeof(double));
+  L.part = o; o += smrf_up256(2 * MAXB * sizeof(double));
   L.red = o; o += 256;
-  L.sc = o; o += align_up(sizeof(Sc));
+  L.sc = o; o += smrf_up256(sizeof(Sc));
   L.total = o;
   return L;
 }

@@ -74,8 +74,6 @@ __global__ __launch_bounds__(256) void mask_apply_kernel(double* __restrict__ Z,
   }
 }
 
-int grid_for(long long n) { return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 8192)); }
-
 }  // namespace
 
 extern "C" {
@@ -83,7 +81,7 @@ extern "C" {
 int smrf_negate_f64(const double* d_in, double* d_out, int64_t n, void* stream) {
   if (n < 0 || (n > 0 && (!d_in || !d_out))) return smrf_fail(SMRF_E_ARG, "null pointer");
   if (n == 0) return SMRF_OK;
-  hipLaunchKernelGGL(negate_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, d_in, d_out, (long long)n);
+  hipLaunchKernelGGL(negate_kernel, dim3(smrf_blocks(n, 8192)), dim3(256), 0, (hipStream_t)stream, d_in, d_out, (long long)n);
   SMRF_LAUNCH_CHECK();
   return SMRF_OK;
 }
@@ -92,7 +90,7 @@ int smrf_mask_apply_f64(double* d_Z, const uint8_t* d_a, const uint8_t* d_b, con
                         int64_t n, void* stream) {
   if (n < 0 || (n > 0 && (!d_Z || !d_a))) return smrf_fail(SMRF_E_ARG, "null pointer");
   if (n == 0) return SMRF_OK;
-  hipLaunchKernelGGL(mask_apply_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, d_Z, d_a, d_b, d_c,
+  hipLaunchKernelGGL(mask_apply_kernel, dim3(smrf_blocks(n, 8192)), dim3(256), 0, (hipStream_t)stream, d_Z, d_a, d_b, d_c,
                      d_union, (long long)n);
   SMRF_LAUNCH_CHECK();
   return SMRF_OK;
@@ -102,8 +100,7 @@ int smrf_gradient_slope_f64(const double* d_Z, double* d_S, int rows, int cols, 
   if (!d_Z || !d_S) return smrf_fail(SMRF_E_ARG, "null pointer");
   if (rows < 2 || cols < 2) return smrf_fail(SMRF_E_ARG, "np.gradient needs at least 2 cells per axis (got %d x %d)", rows, cols);
   const long long n = (long long)rows * cols;
-  const int blocks = (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 8192));
-  hipLaunchKernelGGL(slope_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_Z, d_S, rows, cols, cellsize);
+  hipLaunchKernelGGL(slope_kernel, dim3(smrf_blocks(n, 8192)), dim3(256), 0, (hipStream_t)stream, d_Z, d_S, rows, cols, cellsize);
   SMRF_LAUNCH_CHECK();
   return SMRF_OK;
 }
@@ -114,7 +111,7 @@ int smrf_pssm_f64(const double* d_Z, uint8_t* d_P, double* d_rgba, const double*
   if (d_rgba && !d_lut) return smrf_fail(SMRF_E_ARG, "a colormapped result needs the 256 x 4 table");
   if (rows < 2 || cols < 2) return smrf_fail(SMRF_E_ARG, "np.gradient needs at least 2 cells per axis (got %d x %d)", rows, cols);
   const long long n = (long long)rows * cols;
-  hipLaunchKernelGGL(pssm_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, d_Z, d_P, d_rgba, d_lut, rows,
+  hipLaunchKernelGGL(pssm_kernel, dim3(smrf_blocks(n, 8192)), dim3(256), 0, (hipStream_t)stream, d_Z, d_P, d_rgba, d_lut, rows,
                      cols, cellsize, ve);
   SMRF_LAUNCH_CHECK();
   return SMRF_OK;

@@ -2,8 +2,8 @@
 // cloud with np.histogramdd, thresholds the counts, fills every column below its lowest occupied voxel and pads the
 // bottom).  DESIGN.md section 15 is the contract.
 //
-//   bounds    voxel_bounds_kernel: minimum and maximum per axis and the number of non-finite coordinates of the three
-//             coordinate arrays, one reduction; the host finishes the per-workgroup partials.  No float atomics.
+//   bounds    cloud_reduce.h over XyzLoad: minimum and maximum per axis and the number of non-finite coordinates of the
+//             three coordinate arrays, one reduction; the host finishes the per-workgroup partials.  No float atomics.
 //   mark      voxel_mark_kernel: d = v - min, one rounded subtraction in the cloud's dtype; the bin of d on each axis by
 //             np.histogramdd's rule, settled against the float64 edges the caller uploaded (voxel_bin()); then
 //               threshold == 1  a bit set, one 32-bit word per 32 z-cells, [x][y][word]: the word is loaded and the
@@ -21,16 +21,12 @@
 #include <climits>
 #include <cmath>
 
-#include "smrf_common.h"
+#include "cloud_reduce.h"
 
 namespace smrf {
 
-constexpr int VX_PARTS = 1024;           // workgroups of the bounds reduction at most
-constexpr int VX_PART_VALUES = 7;        // min, max per axis and the non-finite count
 constexpr int VX_TILE_DWORDS = 1024;     // dwords of the output one workgroup of the expand kernel writes: 256 lanes x 4
-static_assert((size_t)VX_PARTS * VX_PART_VALUES * sizeof(double) == SMRF_VOXEL_BOUNDS_BYTES, "smrf_hip.h");
-
-inline size_t vx_up256(size_t v) { return (v + 255) & ~(size_t)255; }
+static_assert(cloud_bytes(3, CLOUD_COUNT, CLOUD_PARTS) == SMRF_VOXEL_BOUNDS_BYTES, "smrf_hip.h");
 
 struct VoxelWs {
   unsigned* marks;   // threshold == 1: [nx * ny * ceil(nz / 32)] words; else [nx * ny * nz] counts
@@ -46,60 +42,20 @@ inline size_t voxel_layout(int nx, int ny, int nz, int threshold, char* base, Vo
   const long long cols = (long long)nx * ny;
   const long long per = threshold == 1 ? vx_words(nz) : (long long)nz;
   if (cols > (long long)INT_MAX || cols > (1ll << 40) || (per > 0 && cols > (1ll << 40) / per)) return 0;
-  const size_t marks = vx_up256((size_t)(cols * per) * 4);
+  const size_t marks = smrf_up256((size_t)(cols * per) * 4);
   if (w) *w = VoxelWs{(unsigned*)base, (int*)(base + marks)};
-  return marks + vx_up256((size_t)cols * 4) + 256;      // never 0 for a volume in range, an empty one included
+  return marks + smrf_up256((size_t)cols * 4) + 256;      // never 0 for a volume in range, an empty one included
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // bounds
 // ---------------------------------------------------------------------------------------------------------------
+// float32 widens to float64 exactly, so cloud_reduce.h's one reduction in float64 serves both dtypes (CLOUD_COUNT)
 template <typename T>
-__global__ __launch_bounds__(256) void voxel_bounds_kernel(const T* __restrict__ x, const T* __restrict__ y,
-                                                           const T* __restrict__ z, long long n,
-                                                           double* __restrict__ part) {
-  // float32 widens to float64 exactly, so one reduction in float64 serves both dtypes; fmin / fmax skip a NaN
-  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  unsigned long long bad = 0;
-  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const double v[3] = {(double)x[i], (double)y[i], (double)z[i]};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      bad += !(fabs(v[a]) < INFINITY);
-      lo[a] = fmin(lo[a], v[a]);
-      hi[a] = fmax(hi[a], v[a]);
-    }
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = fmin(lo[a], __shfl_down(lo[a], o, 64));
-      hi[a] = fmax(hi[a], __shfl_down(hi[a], o, 64));
-    }
-    bad += __shfl_down(bad, o, 64);
-  }
-  __shared__ double s[6][4];
-  __shared__ unsigned long long sbad[4];
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      s[2 * a][w] = lo[a];
-      s[2 * a + 1][w] = hi[a];
-    }
-    sbad[w] = bad;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double* o = part + (long long)blockIdx.x * VX_PART_VALUES;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      o[2 * a] = fmin(fmin(s[2 * a][0], s[2 * a][1]), fmin(s[2 * a][2], s[2 * a][3]));
-      o[2 * a + 1] = fmax(fmax(s[2 * a + 1][0], s[2 * a + 1][1]), fmax(s[2 * a + 1][2], s[2 * a + 1][3]));
-    }
-    o[6] = (double)(sbad[0] + sbad[1] + sbad[2] + sbad[3]);   // < 2^53: exact
-  }
-}
+struct XyzLoad {
+  const T *x, *y, *z;
+  __device__ void operator()(long long i, double* v) const { v[0] = (double)x[i]; v[1] = (double)y[i]; v[2] = (double)z[i]; }
+};
 
 // ---------------------------------------------------------------------------------------------------------------
 // mark
@@ -270,35 +226,13 @@ __global__ __launch_bounds__(256) void voxel_expand_kernel(const unsigned* __res
   }
 }
 
-inline int vx_blocks(long long n, int cap) { return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, cap)); }
-
 template <typename T>
 int voxel_bounds(const T* d_x, const T* d_y, const T* d_z, int64_t n, double* h_box, int64_t* h_nonfinite,
                  void* d_workspace, size_t workspace_bytes, hipStream_t stream) {
   if (n < 1 || n > (int64_t)INT_MAX) return smrf_fail(SMRF_E_ARG, "%lld points: 1 to 2^31 - 1 expected", (long long)n);
   if (!d_x || !d_y || !d_z || !h_box || !h_nonfinite) return smrf_fail(SMRF_E_ARG, "null pointer");
-  if (!d_workspace || workspace_bytes < (size_t)SMRF_VOXEL_BOUNDS_BYTES)
-    return smrf_fail(SMRF_E_WORKSPACE, "bounds workspace of %zu bytes, %d needed", workspace_bytes, SMRF_VOXEL_BOUNDS_BYTES);
-  const int blocks = vx_blocks(n, VX_PARTS);
-  double* part = (double*)d_workspace;
-  hipLaunchKernelGGL(voxel_bounds_kernel<T>, dim3(blocks), dim3(256), 0, stream, d_x, d_y, d_z, (long long)n, part);
-  SMRF_LAUNCH_CHECK();
-  static thread_local double host[VX_PARTS * VX_PART_VALUES];
-  SMRF_HIP_CHECK(hipMemcpyAsync(host, part, (size_t)blocks * VX_PART_VALUES * sizeof(double), hipMemcpyDeviceToHost, stream));
-  SMRF_HIP_CHECK(hipStreamSynchronize(stream));
-  double r[6] = {INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY};
-  double bad = 0.0;
-  for (int b = 0; b < blocks; ++b) {
-    const double* p = host + b * VX_PART_VALUES;
-    for (int a = 0; a < 3; ++a) {
-      r[2 * a] = std::min(r[2 * a], p[2 * a]);
-      r[2 * a + 1] = std::max(r[2 * a + 1], p[2 * a + 1]);
-    }
-    bad += p[6];
-  }
-  for (int k = 0; k < 6; ++k) h_box[k] = r[k];
-  *h_nonfinite = (int64_t)bad;
-  return SMRF_OK;
+  return cloud_bounds<3, 3, CLOUD_COUNT>(XyzLoad<T>{d_x, d_y, d_z}, n, h_box, h_nonfinite, d_workspace, workspace_bytes,
+                                         (size_t)SMRF_VOXEL_BOUNDS_BYTES, stream);
 }
 
 template <typename T>
@@ -316,7 +250,7 @@ int voxel_mark(const T* d_x, const T* d_y, const T* d_z, int64_t n, const double
   if (nx == 0 || ny == 0 || nz == 0) return SMRF_OK;       // no bins: every sample is dropped
   const long long entries = (long long)nx * ny * (threshold == 1 ? vx_words(nz) : (long long)nz);
   SMRF_HIP_CHECK(hipMemsetAsync(w.marks, 0, (size_t)entries * 4, stream));
-  const int blocks = vx_blocks(n, 16384);
+  const int blocks = smrf_blocks(n, 16384);
   const T ox = (T)h_offsets[0], oy = (T)h_offsets[1], oz = (T)h_offsets[2];
   if (threshold == 1)
     hipLaunchKernelGGL((voxel_mark_kernel<T, false>), dim3(blocks), dim3(256), 0, stream, d_x, d_y, d_z, (long long)n, ox,

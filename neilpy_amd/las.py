@@ -146,6 +146,7 @@ def read_las_xyz(filename):
     import os
     import torch
     from . import _lib
+    from ._raster import _ptr, _stream
     _lib.require_gpu()
     size = os.path.getsize(filename)
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -174,9 +175,7 @@ def read_las_xyz(filename):
                 k += 1
     out = [torch.empty(npts, dtype=torch.float64, device=dev) for _ in range(3)]
     so = (C.c_double * 6)(*(list(header['scale']) + list(header['offset'])))
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    _lib.check(_lib.load().smrf_las_decode_xyz_f64(C.c_void_p(buf.data_ptr()), npts, reclen, so,
-                                                   *(C.c_void_p(t.data_ptr()) for t in out), st))
+    _lib.check(_lib.load().smrf_las_decode_xyz_f64(_ptr(buf), npts, reclen, so, *(_ptr(t) for t in out), _stream()))
     return (header,) + tuple(out)
 
 

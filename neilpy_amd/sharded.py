@@ -24,7 +24,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _cloud, _lib
+from ._raster import _ptr, _stream, _suffix
 
 __all__ = ["band_rows", "window_groups", "HipBandOps", "progressive_filter_sharded", "HipSpringsOps",
            "inpaint_nans_by_springs_sharded", "create_dem_band", "HipPointOps", "create_dem_sharded", "smrf_sharded"]
@@ -45,22 +46,12 @@ class HipBandOps:
         _lib.require_gpu()
         self.impl = impl
 
-    @staticmethod
-    def _sfx(t):
-        import torch
-        return "f32" if t.dtype == torch.float32 else "f64"
-
-    @staticmethod
-    def _stream():
-        import torch
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
     def has_nan(self, band):
         """NaNs in this rank's rows?  (scipy's filters let the first visited footprint element decide NaN-ness; the
         kernels follow that rule only when told to, so the driver asks once per call and all-reduces the answer)"""
         cnt = C.c_int64(0)
-        fn = getattr(self.lib, "smrf_count_nan_" + self._sfx(band))
-        _lib.check(fn(C.c_void_p(band.data_ptr()), band.numel(), C.byref(cnt), self._stream()))
+        fn = getattr(self.lib, "smrf_count_nan_" + _suffix(band))
+        _lib.check(fn(_ptr(band), band.numel(), C.byref(cnt), _stream()))
         return cnt.value > 0
 
     def can_fuse(self, t, radius):
@@ -81,39 +72,35 @@ class HipBandOps:
     def chain_flag(self, last, last_row0, opened, mask, when, radii, thr, widx, out_row0, out_rows, img_rows):
         """the windows ``radii`` opened one after the other in ONE launch: ``opened`` = the last surface on global rows
         [out_row0, out_row0 + out_rows), every window's flags on those rows; ``last`` reaches sum(2r) rows beyond them"""
-        fn = getattr(self.lib, "smrf_pf_chain_flag_" + self._sfx(last))
+        fn = getattr(self.lib, "smrf_pf_chain_flag_" + _suffix(last))
         cols = last.shape[1]
         r = np.ascontiguousarray(np.asarray(radii, dtype=np.int32))
         t = np.ascontiguousarray(np.asarray(thr, dtype=np.float64))
         w = np.ascontiguousarray(np.asarray(widx, dtype=np.int32))
-        _lib.check(fn(C.c_void_p(last.data_ptr()), C.c_void_p(opened.data_ptr()), C.c_void_p(mask.data_ptr()),
-                      C.c_void_p(when.data_ptr()) if when is not None else C.c_void_p(0), r.ctypes.data_as(C.c_void_p),
+        _lib.check(fn(_ptr(last), _ptr(opened), _ptr(mask), _ptr(when), r.ctypes.data_as(C.c_void_p),
                       t.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p), int(r.size), img_rows, cols, cols, last_row0,
-                      last.shape[0], out_row0, out_rows, self._stream()))
+                      last.shape[0], out_row0, out_rows, _stream()))
 
     def open_flag(self, last, last_row0, opened, mask, when, thr, widx, out_row0, out_rows, img_rows, radius):
         """opened = opening(last, disk(r)) on global rows [out_row0, out_row0 + out_rows) + the flag step, one launch;
         ``last`` holds global rows from ``last_row0`` and reaches 2r rows beyond the outputs"""
-        fn = getattr(self.lib, "smrf_pf_open_flag_" + self._sfx(last))
+        fn = getattr(self.lib, "smrf_pf_open_flag_" + _suffix(last))
         cols = last.shape[1]
-        _lib.check(fn(C.c_void_p(last.data_ptr()), C.c_void_p(opened.data_ptr()), C.c_void_p(mask.data_ptr()),
-                      C.c_void_p(when.data_ptr()) if when is not None else C.c_void_p(0), float(thr), int(widx), img_rows, cols,
-                      cols, last_row0, last.shape[0], out_row0, out_rows, int(radius), self._stream()))
+        _lib.check(fn(_ptr(last), _ptr(opened), _ptr(mask), _ptr(when), float(thr), int(widx), img_rows, cols, cols,
+                      last_row0, last.shape[0], out_row0, out_rows, int(radius), _stream()))
 
     def erode(self, src, src_row0, dst, dst_row0, dst_rows, img_rows, radius, nan_aware=0):
-        fn = getattr(self.lib, "smrf_disk_filter_" + self._sfx(src))
-        _lib.check(fn(C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()), img_rows, src.shape[1], src.shape[1],
-                      src_row0, src.shape[0], dst_row0, dst_rows, int(radius), 0, int(nan_aware), self.impl, self._stream()))
+        fn = getattr(self.lib, "smrf_disk_filter_" + _suffix(src))
+        _lib.check(fn(_ptr(src), _ptr(dst), img_rows, src.shape[1], src.shape[1], src_row0, src.shape[0], dst_row0,
+                      dst_rows, int(radius), 0, int(nan_aware), self.impl, _stream()))
 
     def dilate_flag(self, eroded, er_row0, er_rows, last_band, opened_band, mask, when, thr, widx, band_row0,
                     band_nrows, img_rows, radius, nan_aware=0):
-        fn = getattr(self.lib, "smrf_pf_dilate_flag_" + self._sfx(eroded))
+        fn = getattr(self.lib, "smrf_pf_dilate_flag_" + _suffix(eroded))
         cols = eroded.shape[1]
-        _lib.check(fn(C.c_void_p(eroded.data_ptr()), C.c_void_p(last_band.data_ptr()),
-                      C.c_void_p(opened_band.data_ptr()), C.c_void_p(mask.data_ptr()),
-                      C.c_void_p(when.data_ptr()) if when is not None else C.c_void_p(0), float(thr), int(widx),
+        _lib.check(fn(_ptr(eroded), _ptr(last_band), _ptr(opened_band), _ptr(mask), _ptr(when), float(thr), int(widx),
                       img_rows, cols, cols, er_row0, er_rows, band_row0, band_nrows, int(radius), int(nan_aware), self.impl,
-                      self._stream()))
+                      _stream()))
 
 
 def _exchange(dist, group, rank, world, send_up, recv_up, send_down, recv_down):
@@ -401,23 +388,19 @@ class HipSpringsOps:
         self.red2 = self.ws[lay[4]:lay[4] + 16].view(torch.float64)      # [|v|^2, |dk|^2] of the ATUXW phase
         self.red = self.red2[:1]                                          # the single sum of the other phases
 
-    def _stream(self):
-        import torch
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
     def begin(self, atol, btol, conlim, iter_lim):
         _lib.check(self.lib.smrf_springs_band_begin(self.rows, self.cols, atol, btol, conlim, iter_lim,
-                                                    C.c_void_p(self.ws.data_ptr()), self.nbytes, self._stream()))
+                                                    _ptr(self.ws), self.nbytes, _stream()))
 
     def phase(self, ph):
-        _lib.check(self.lib.smrf_springs_band_phase(ph, C.c_void_p(self.A.data_ptr()), self.rows, self.cols,
-                                                    self.flags[0], self.flags[1], C.c_void_p(self.ws.data_ptr()),
-                                                    self.nbytes, self._stream()))
+        _lib.check(self.lib.smrf_springs_band_phase(ph, _ptr(self.A), self.rows, self.cols,
+                                                    self.flags[0], self.flags[1], _ptr(self.ws),
+                                                    self.nbytes, _stream()))
 
     def status(self):
         istop, itn, nunk, done = C.c_int(0), C.c_int64(0), C.c_int64(0), C.c_int(0)
-        _lib.check(self.lib.smrf_springs_band_status(C.c_void_p(self.ws.data_ptr()), self.rows, self.cols, C.byref(istop),
-                                                     C.byref(itn), C.byref(nunk), C.byref(done), self._stream()))
+        _lib.check(self.lib.smrf_springs_band_status(_ptr(self.ws), self.rows, self.cols, C.byref(istop),
+                                                     C.byref(itn), C.byref(nunk), C.byref(done), _stream()))
         return istop.value, itn.value, nunk.value, bool(done.value)
 
 
@@ -530,23 +513,8 @@ def create_dem_band(xd, yd, zd, inv_affine, grid_shape, *, rank, world_size, bin
     The binning kernel takes the band as (row0, rows_local) and ignores points of other bands, so N
     ranks read the points N times but write disjoint rows (the all-to-all of points by
     destination band is the alternative when the points do not fit every rank)."""
-    import torch
-    lib = _lib.load()
-    ny, nx = grid_shape
-    b0, b1 = band_rows(ny, world_size, rank)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    keys = torch.empty((b1 - b0, nx), dtype=torch.int64, device=xd.device)
-    n_out = torch.zeros(1, dtype=torch.int64, device=xd.device)
-    grid = torch.empty((b1 - b0, nx), dtype=torch.float64, device=xd.device)
-    empty = torch.empty((b1 - b0, nx), dtype=torch.uint8, device=xd.device)
-    h_inv = (C.c_double * 6)(*[float(v) for v in inv_affine])
-    is_max = 1 if bin_type == 'max' else 0
-    p = lambda t: C.c_void_p(t.data_ptr())
-    _lib.check(lib.smrf_grid_clear_u64(p(keys), keys.numel(), st))
-    _lib.check(lib.smrf_grid_bin_f64(p(xd), p(yd), p(zd), xd.numel(), h_inv, None, p(keys), ny, nx, b0, b1 - b0, is_max,
-                                     p(n_out), st))
-    _lib.check(lib.smrf_grid_finalize_f64(p(keys), p(grid), p(empty), keys.numel(), is_max, st))
-    return grid, empty, int(n_out.item())
+    b0, b1 = band_rows(grid_shape[0], world_size, rank)
+    return _cloud.grid_rows(xd, yd, zd, inv_affine, grid_shape, b0, b1 - b0, bin_type)
 
 
 class HipPointOps:
@@ -556,51 +524,26 @@ class HipPointOps:
         self.lib = _lib.load()
         _lib.require_gpu()
 
-    @staticmethod
-    def _st():
-        import torch
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
     def extent(self, xd, yd):
         """(xmin, xmax, ymin, ymax) of this rank's points; (+inf, -inf, +inf, -inf) for none"""
-        import torch
-        if xd.numel() == 0:
-            return (np.inf, -np.inf, np.inf, -np.inf)
-        ws = torch.empty(4 * 1024, dtype=torch.float64, device=xd.device)
-        ext = (C.c_double * 4)()
-        _lib.check(self.lib.smrf_points_extent_f64(C.c_void_p(xd.data_ptr()), C.c_void_p(yd.data_ptr()), xd.numel(), ext,
-                                                   C.c_void_p(ws.data_ptr()), ws.numel() * 8, self._st()))
-        return tuple(float(v) for v in ext)
+        return _cloud.extent(xd, yd)
 
     def bucket(self, xd, yd, zd, inv, rows_total, nbands):
         """points grouped by destination row band: (counts int64[nbands] on the device, x, y, z packed runs)"""
         import torch
         h_inv = (C.c_double * 6)(*[float(v) for v in inv])
-        p = lambda t: C.c_void_p(t.data_ptr())                  # noqa: E731
         counts = torch.zeros(nbands, dtype=torch.int64, device=xd.device)
-        _lib.check(self.lib.smrf_points_band_count_f64(p(xd), p(yd), xd.numel(), h_inv, rows_total, nbands, p(counts), self._st()))
+        _lib.check(self.lib.smrf_points_band_count_f64(_ptr(xd), _ptr(yd), xd.numel(), h_inv, rows_total, nbands,
+                                                       _ptr(counts), _stream()))
         cursors = torch.cumsum(counts, 0) - counts               # exclusive prefix sum: each band's first slot
         ox, oy, oz = torch.empty_like(xd), torch.empty_like(yd), torch.empty_like(zd)
-        _lib.check(self.lib.smrf_points_band_pack_f64(p(xd), p(yd), p(zd), xd.numel(), h_inv, rows_total, nbands, p(cursors),
-                                                      p(ox), p(oy), p(oz), self._st()))
+        _lib.check(self.lib.smrf_points_band_pack_f64(_ptr(xd), _ptr(yd), _ptr(zd), xd.numel(), h_inv, rows_total, nbands,
+                                                      _ptr(cursors), _ptr(ox), _ptr(oy), _ptr(oz), _stream()))
         return counts, ox, oy, oz
 
     def bin_band(self, xd, yd, zd, inv, grid_shape, row0, rows_local, bin_type):
         """(float64 band, uint8 empty mask, points outside the raster) from the points this rank received"""
-        import torch
-        ny, nx = grid_shape
-        p = lambda t: C.c_void_p(t.data_ptr())                  # noqa: E731
-        keys = torch.empty((rows_local, nx), dtype=torch.int64, device=xd.device)
-        n_out = torch.zeros(1, dtype=torch.int64, device=xd.device)
-        grid = torch.empty((rows_local, nx), dtype=torch.float64, device=xd.device)
-        empty = torch.empty((rows_local, nx), dtype=torch.uint8, device=xd.device)
-        h_inv = (C.c_double * 6)(*[float(v) for v in inv])
-        is_max = 1 if bin_type == 'max' else 0
-        _lib.check(self.lib.smrf_grid_clear_u64(p(keys), keys.numel(), self._st()))
-        _lib.check(self.lib.smrf_grid_bin_f64(p(xd), p(yd), p(zd), xd.numel(), h_inv, None, p(keys), ny, nx, row0, rows_local,
-                                              is_max, p(n_out), self._st()))
-        _lib.check(self.lib.smrf_grid_finalize_f64(p(keys), p(grid), p(empty), keys.numel(), is_max, self._st()))
-        return grid, empty, int(n_out.item())
+        return _cloud.grid_rows(xd, yd, zd, inv, grid_shape, row0, rows_local, bin_type)
 
 
 def _a2a(dist, group, out, inp, out_splits, in_splits):
@@ -737,8 +680,6 @@ def smrf_sharded(x, y, z, cellsize=1, windows=5, slope_threshold=.15, elevation_
         windows = np.arange(windows) + 1
     windows = np.asarray(windows)
     lib = _lib.load()
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)    # noqa: E731
-    st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)              # noqa: E731
     if points not in ("replicated", "sharded"):
         raise ValueError("points must be 'replicated' or 'sharded'")
     xd, yd, zd = api._points_to_device(x, y, z)
@@ -757,19 +698,20 @@ def smrf_sharded(x, y, z, cellsize=1, windows=5, slope_threshold=.15, elevation_
             raise ValueError("invalid entry in coordinates array")
     stats = {"inpaint1": inpaint_nans_by_springs_sharded(band, ny, rank=rank, world_size=world_size, group=group)}
     neg = torch.empty_like(band)
-    _lib.check(lib.smrf_negate_f64(p(band), p(neg), band.numel(), st()))
+    _lib.check(lib.smrf_negate_f64(_ptr(band), _ptr(neg), band.numel(), _stream()))
     low, _ = progressive_filter_sharded(neg, ny, np.array([1]), low_filter_slope * (np.array([1]) * cellsize),
                                         rank=rank, world_size=world_size, group=group)                 # :1744
     low = low.clone()
     del neg
     if low_outlier_fill:                                                           # :1747-1749
-        _lib.check(lib.smrf_mask_apply_f64(p(band), p(low), None, None, None, band.numel(), st()))
+        _lib.check(lib.smrf_mask_apply_f64(_ptr(band), _ptr(low), None, None, None, band.numel(), _stream()))
         stats["inpaint1b"] = inpaint_nans_by_springs_sharded(band, ny, rank=rank, world_size=world_size, group=group)
     obj, _ = progressive_filter_sharded(band, ny, windows, slope_threshold * (windows * cellsize), rank=rank,
                                         world_size=world_size, group=group)        # :1752-1755
     obj = obj.contiguous()
     object_cells = torch.empty_like(obj)
-    _lib.check(lib.smrf_mask_apply_f64(p(band), p(empty), p(low), p(obj), p(object_cells), band.numel(), st()))   # :1762-1763
+    _lib.check(lib.smrf_mask_apply_f64(_ptr(band), _ptr(empty), _ptr(low), _ptr(obj), _ptr(object_cells), band.numel(),
+                                       _stream()))                                 # :1762-1763
     stats["inpaint2"] = inpaint_nans_by_springs_sharded(band, ny, rank=rank, world_size=world_size, group=group)  # :1764
     # tail: the spline needs the whole DTM; the points are split evenly
     sizes = [band_rows(ny, world_size, k)[1] - band_rows(ny, world_size, k)[0] for k in range(world_size)]

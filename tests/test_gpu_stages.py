@@ -114,6 +114,119 @@ def test_points_extent_short_workspace(lib, gpu_device):
     assert _extent(lib, gpu_device, x, x, 4 * 1024 * 8 - 1)[0] == E_WORKSPACE
 
 
+# ------------------------------------------------------------------- smrf_points_nn_bounds_f64, smrf_voxel_bounds_f32/64
+# the other two callers of csrc/cloud_reduce.h: non-finite coordinates are counted, the box skips a NaN and takes an
+# infinity.  Their loop is capped at 1024 workgroups, so the last length reaches its second trip.
+PARTS_LENGTHS = LENGTHS[:-1] + [1024 * 256 + 257]
+
+
+def _box_numpy(cols, n):
+    """(min, max) per column as float64.  np.nanmin / np.nanmax, which a column of one NaN (n = 1) has none of: the
+    reduction then leaves its identity, (inf, -inf)"""
+    out = []
+    for c in cols:
+        c = c.astype(np.float64)
+        if n > 1:
+            assert np.fmin.reduce(c) == np.nanmin(c) and np.fmax.reduce(c) == np.nanmax(c)
+        out += [np.fmin.reduce(c, initial=np.inf), np.fmax.reduce(c, initial=-np.inf)]
+    return np.array(out)
+
+
+def _nn_bounds(lib, gpu_device, pts, ws_bytes=1024 * 5 * 8):
+    import torch
+    ws = torch.full((max(ws_bytes, 1),), 255, dtype=torch.uint8, device=gpu_device)
+    box, bad = doubles(0, 0, 0, 0), C.c_int64(-7)
+    pts_d = dev(pts, gpu_device)
+    rc = lib.smrf_points_nn_bounds_f64(p(pts_d), pts.shape[0], pts.shape[1], box, C.byref(bad), p(ws), ws_bytes, stream())
+    return rc, np.array(box[:]), bad.value
+
+
+@pytest.mark.parametrize("dim", [2, 3])
+@pytest.mark.parametrize("n", PARTS_LENGTHS)
+def test_points_nn_bounds(lib, gpu_device, n, dim):
+    rng = np.random.default_rng(n + dim)
+    pts = rng.normal(8.6e5, 300.0, (n, dim))
+    pts[:, dim - 1] *= 3.0                                            # the last column reaches past the others
+    rc, box, bad = _nn_bounds(lib, gpu_device, pts)
+    assert rc == 0 and bad == 0
+    assert same_bits(box, np.array([pts[:, 0].min(), pts[:, 0].max(), pts[:, 1].min(), pts[:, 1].max()]))
+    # NaN and +-inf are counted over all columns; the box is of columns 0 and 1, skips the NaN and takes the infinity
+    pts[0, 0] = np.nan
+    pts[n // 2, 1] = np.inf
+    if dim == 3:
+        pts[n - 1, 2] = -np.inf
+    rc, box, bad = _nn_bounds(lib, gpu_device, pts)
+    assert rc == 0 and bad == dim
+    assert same_bits(box, _box_numpy([pts[:, 0], pts[:, 1]], n)) and box[3] == np.inf and box[2] != -np.inf
+
+
+def test_points_nn_bounds_signed_zero(lib, gpu_device):
+    """min0 over (0.0, -0.0, 1.0, ...) is a zero whose sign the order of the reduction decides: lane 0 holds +0.0,
+    lane 1 -0.0, and the last step of the shuffle tree is fmin(+0.0, -0.0) = -0.0 on gfx950.  The sign asserted is
+    the one points_bounds_kernel returned before the bounds kernels became one (profiles/cloud_boundary.md section 2)"""
+    pts = np.ones((1000, 2))
+    pts[0, 0], pts[1, 0] = 0.0, -0.0
+    rc, box, bad = _nn_bounds(lib, gpu_device, pts)
+    print("min0 = %r, signbit %s" % (box[0], np.signbit(box[0])))
+    assert rc == 0 and bad == 0 and same_bits(box, np.array([-0.0, 1.0, 1.0, 1.0]))
+
+
+def test_points_nn_bounds_short_workspace(lib, gpu_device):
+    pts = np.arange(2000.0).reshape(1000, 2)
+    assert _nn_bounds(lib, gpu_device, pts, 1024 * 5 * 8)[0] == 0
+    rc, box, bad = _nn_bounds(lib, gpu_device, pts, 1024 * 5 * 8 - 1)
+    assert rc == E_WORKSPACE and np.array_equal(box, np.zeros(4)) and bad == -7     # refused before any launch
+
+
+def _voxel_bounds(lib, gpu_device, x, y, z, ws_bytes=57344):
+    import torch
+    ws = torch.full((max(ws_bytes, 1),), 255, dtype=torch.uint8, device=gpu_device)
+    box, bad = doubles(0, 0, 0, 0, 0, 0), C.c_int64(-7)
+    x_d, y_d, z_d = dev(x, gpu_device), dev(y, gpu_device), dev(z, gpu_device)
+    fn = lib.smrf_voxel_bounds_f32 if x.dtype == np.float32 else lib.smrf_voxel_bounds_f64
+    rc = fn(p(x_d), p(y_d), p(z_d), x.size, box, C.byref(bad), p(ws), ws_bytes, stream())
+    return rc, np.array(box[:]), bad.value
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("n", PARTS_LENGTHS)
+def test_voxel_bounds(lib, gpu_device, n, dtype):
+    rng = np.random.default_rng(n)
+    x, y, z = (rng.normal(c, 300.0, n).astype(dtype) for c in (8.6e5, 1.9e6, 120.0))
+    rc, box, bad = _voxel_bounds(lib, gpu_device, x, y, z)
+    assert rc == 0 and bad == 0
+    assert same_bits(box, np.array([x.min(), x.max(), y.min(), y.max(), z.min(), z.max()], dtype=np.float64))
+    x[0] = np.nan
+    y[n // 2] = np.inf
+    z[n - 1] = -np.inf
+    rc, box, bad = _voxel_bounds(lib, gpu_device, x, y, z)
+    assert rc == 0 and bad == 3
+    assert same_bits(box, _box_numpy([x, y, z], n)) and box[3] == np.inf and box[4] == -np.inf
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_voxel_bounds_signed_zero(lib, gpu_device, dtype):
+    """zeros of both signs at the ends of a column: the box holds what voxel_bounds_kernel returned for this input
+    before the bounds kernels became one (profiles/cloud_boundary.md section 2): -0.0 for both minima whichever zero
+    comes first, and -0.0 for the maximum of z, whose +0.0 sits in the last row"""
+    n = 1000
+    x, y, z = np.ones(n, dtype), np.ones(n, dtype), -np.ones(n, dtype)
+    x[0], x[1] = 0.0, -0.0
+    y[0], y[1] = -0.0, 0.0
+    z[0], z[n - 1] = -0.0, 0.0
+    rc, box, bad = _voxel_bounds(lib, gpu_device, x, y, z)
+    print("box = %r, signbit %s" % (box, np.signbit(box)))
+    assert rc == 0 and bad == 0 and same_bits(box, np.array([-0.0, 1.0, -0.0, 1.0, -1.0, -0.0]))
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_voxel_bounds_short_workspace(lib, gpu_device, dtype):
+    x = np.arange(1000, dtype=dtype)
+    assert _voxel_bounds(lib, gpu_device, x, x, x, 57344)[0] == 0
+    rc, box, bad = _voxel_bounds(lib, gpu_device, x, x, x, 57344 - 1)
+    assert rc == E_WORKSPACE and np.array_equal(box, np.zeros(6)) and bad == -7       # refused before any launch
+
+
 # ----------------------------------------------------------------------------------------------- smrf_affine_apply_f64
 def _inverse(cellsize, theta, x0=8.6e5, y0=1.9e6):
     """(a, b, c, d, e, f) of the inverse of a north-up (theta = 0) or rotated transform with its origin at (x0, y0)"""

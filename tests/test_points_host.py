@@ -153,8 +153,8 @@ def test_points_kernels_compile_without_scratch(tmp_path):
     instructions, and the only atomics are the sort's integer counters (no GPU needed)"""
     text, kernels = device_asm("points", tmp_path)
     names = sorted(kernels)
-    assert len(names) == 9, names      # bounds, count, scan x 3, scatter, search x 2 dimensions, sum
-    for stem, n in (("points_bounds_kernel", 1), ("points_count_kernel", 1), ("points_scan_", 3),
+    assert len(names) == 10, names     # bounds x 2 dimensions, count, scan x 3, scatter, search x 2 dimensions, sum
+    for stem, n in (("cloud_bounds_kernel", 2), ("points_count_kernel", 1), ("points_scan_", 3),
                     ("points_scatter_kernel", 1), ("points_search_kernel", 2), ("points_sum_kernel", 1)):
         assert sum(stem in k for k in names) == n, (stem, names)
     assert_no_scratch(text, kernels)

@@ -114,7 +114,7 @@ def test_one_definition_of_the_boundary():
         if os.path.basename(path) == "_raster.py":
             continue
         defs = {n.name for n in ast.walk(ast.parse(open(path).read())) if isinstance(n, ast.FunctionDef)}
-        assert not defs & {"_raster", "_out", "_empty", "_check_2d"}, path
+        assert not defs & {"_raster", "_out", "_empty", "_check_2d", "_stream", "_sfx", "_st", "_ptr", "_suffix"}, path
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])

@@ -46,8 +46,8 @@ def kernel_resources():
         def num(key):
             return int(re.search(re.escape(key) + r":?\s*(?:\[[^\]]*\]:\s*)?(\d+)", block).group(1))
         name = re.sub(r"^_ZN4smrf\d+", "", block.split()[0])
-        m = re.match(r"(points_\w+?_kernel)(ILi(\d)E)?", name)
-        rows.append((m.group(1) + ("<%s>" % m.group(3) if m.group(3) else ""), num("VGPRs"), num("TotalSGPRs"),
+        m = re.match(r"((?:points|cloud)_\w+?_kernel)(?:\w*?ILi(\d)E)?", name)   # <dimension>: its own, or its loader's
+        rows.append((m.group(1) + ("<%s>" % m.group(2) if m.group(2) else ""), num("VGPRs"), num("TotalSGPRs"),
                      num("LDS Size [bytes/block]"), num("ScratchSize [bytes/lane]"), num("Occupancy [waves/SIMD]")))
     return rows
 
