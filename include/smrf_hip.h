@@ -138,7 +138,7 @@ SMRF_API int smrf_pf_dilate_flag_f64(const double* d_eroded, const double* d_las
  * in_row0 + in_rows - 1; d_opened, d_mask, d_when_dropped address global row out_row0; the same `last` values
  * are used for the flag comparison.  d_mask may be NULL (opening only).  No NaN rule: the caller must not hand
  * it rasters with NaNs.  Returns SMRF_E_UNSUPPORTED for radii without a fused kernel
- * (smrf_fused_open_supported tells which: fp32 1..8 and 10..14, fp64 1..6). */
+ * (smrf_fused_open_supported tells which: fp32 1..8 and 10..14, fp64 1..6; csrc/pf_route.h). */
 SMRF_API int smrf_fused_open_supported(int elem_size, int radius);
 SMRF_API int smrf_pf_open_flag_f32(const float* d_last, float* d_opened, uint8_t* d_mask, uint8_t* d_when_dropped,
                           double threshold, int window_index, int img_rows, int cols, int64_t ld, int in_row0,
@@ -153,7 +153,7 @@ SMRF_API int smrf_pf_open_flag_f64(const double* d_last, double* d_opened, uint8
  * smrf_pf_open_flag_* calls would.  Replaces n iterations of the loop of neilpy/neilpy.py:1667-1676.  Row-band form: the band
  * of `last` must reach sum(2 * radius) rows (reflected at the raster's true borders) beyond the output rows; flags are
  * written for the output rows only.  No NaN rule.  smrf_pf_chain_length: how many of the windows at the head of h_radii one
- * launch takes on a raster of raster_cells cells (0: none; e.g. 3 for 1, 2, 3, ...; 1 = a table-free single launch);
+ * launch takes on a raster of raster_cells cells (0: none; e.g. 3 for 1, 2, 3, ...; 1 = a table-free single launch; the pattern table of csrc/pf_route.h);
  * smrf_pf_chain_flag_* returns SMRF_E_UNSUPPORTED unless n_windows is a length this function reports for those radii
  * at some raster size. */
 SMRF_API int smrf_pf_chain_length(int elem_size, const int32_t* h_radii, int n, int64_t raster_cells);
@@ -206,6 +206,19 @@ SMRF_API int smrf_progressive_filter_timed_f64(const double* d_Z, int rows, int 
  * 0 never / 1 per measured table / 2 always).  Writes n bytes (0 / 1; 0 beyond the call's windows) and returns the
  * call's window count.  Such a window still reports SMRF_ROUTE_TWO_PASS: it is two launches, 3s + (3s + 2) B/cell. */
 SMRF_API int smrf_pf_ero_inc_windows(uint8_t* h_taken, int n);
+
+/* The launch plan of progressive_filter, without running anything (host logic, no device needed; csrc/pf_route.h is the single
+ * statement of the rule): h_route[i] = the SMRF_ROUTE_* that smrf_progressive_filter_timed_* reports for window i of the n
+ * h_windows on a `rows`-row raster of `cells` cells, h_ero_inc[i] = what smrf_pf_ero_inc_windows reports, under the library's
+ * SMRF_FUSED / SMRF_CHAIN / SMRF_ERO_INC switches.  nan_aware: 0 = a raster without NaN, anything else = one that may hold
+ * some (a call with nan_aware < 0 finds out which and then follows that plan).  band = 0: the whole-raster call.  band = 1: the
+ * row-band driver (neilpy_amd/sharded.py) - rows = the image's rows, cells = what one launch marches (the longest band with its
+ * two-sided margin); the launch at the head of the list is h_route[0], smrf_pf_chain_flag_* when it reads SMRF_ROUTE_CHAIN
+ * (with the windows that read SMRF_ROUTE_CHAIN + 1, + 2 after it), smrf_pf_open_flag_* for SMRF_ROUTE_FUSED, else the two
+ * passes; a band takes fused openings up to radius 8 only and no incremental erosion.  band = 2: a row band whose launches
+ * cannot be chained either (one split edge-first, or a single band). */
+SMRF_API int smrf_pf_plan(int elem_size, const int32_t* h_windows, int n, int rows, int64_t cells, int nan_aware, int impl,
+                 int band, int32_t* h_route, uint8_t* h_ero_inc);
 
 /* number of NaN cells of a contiguous array, written to *h_count (synchronises `stream`) */
 SMRF_API int smrf_count_nan_f32(const float* d_a, int64_t n, int64_t* h_count, void* stream);

@@ -58,6 +58,7 @@ SIGNATURES = {
     "smrf_progressive_filter_timed_f32": (_i, [_p, _i, _i, _p, _p, _i, _p, _p, _p, _sz, _i, _i, _p, _p, _p]),
     "smrf_progressive_filter_timed_f64": (_i, [_p, _i, _i, _p, _p, _i, _p, _p, _p, _sz, _i, _i, _p, _p, _p]),
     "smrf_pf_ero_inc_windows": (_i, [_p, _i]),
+    "smrf_pf_plan": (_i, [_i, _p, _i, _i, _i64, _i, _i, _i, _p, _p]),
     "smrf_count_nan_f32": (_i, [_p, _i64, C.POINTER(_i64), _p]),
     "smrf_count_nan_f64": (_i, [_p, _i64, C.POINTER(_i64), _p]),
     "smrf_points_extent_f64": (_i, [_p, _p, _i64, C.POINTER(_d), _p, _sz, _p]),

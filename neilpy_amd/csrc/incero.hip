@@ -6,13 +6,6 @@ template <int R>
 int launch_r(const smrf::IncEroArgs<float>& a, hipStream_t s) { return smrf::inc_erode_launch<float, R>(a, s); }
 }  // namespace
 
-bool smrf_inc_erode_has(int elem_size, int radius) {
-  return elem_size == 4 && radius >= SMRF_INCERO_MIN_RADIUS && radius <= SMRF_INCERO_MAX_RADIUS;
-}
-bool smrf_inc_erode_adopted(int elem_size, int radius) {
-  return smrf_inc_erode_has(elem_size, radius) && smrf::kEroIncAdoptF32[radius] != 0;
-}
-
 int smrf_inc_erode_f32(const float* e_prev, const float* last, float* out, int rows, int cols, long long ld, int radius, int nt,
                        hipStream_t s) {
   smrf::IncEroArgs<float> a{};

@@ -159,13 +159,22 @@ int nt_rule(int img_rows, int cols) {
   return (size_t)img_rows * (size_t)cols * sizeof(T) >= ((size_t)192 << 20);
 }
 
+// the row band of a launch (smrf_hip.h: input rows [in_row0, in_row0 + in_rows), output rows [out_row0, out_row0 + out_rows) of
+// an img_rows x cols raster) and its store kind, into a DiskArgs<T> or a ChainArgs<T>
+template <typename T, template <typename> class Args>
+void set_band(Args<T>& a, int img_rows, int cols, int64_t ld, int in_row0, int in_rows, int out_row0, int out_rows) {
+  a.img_rows = img_rows; a.cols = cols; a.ld = ld;
+  a.in_row0 = in_row0; a.in_rows = in_rows; a.out_row0 = out_row0; a.out_rows = out_rows;
+  a.nt = nt_rule<T>(img_rows, cols);
+}
+
 template <typename T>
 int disk_filter_api(const T* in, T* out, int img_rows, int cols, int64_t ld, int in_row0, int in_rows,
                     int out_row0, int out_rows, int radius, int is_dilate, int nan_aware, int impl, void* stream) {
   DiskArgs<T> a{};
-  a.in = in; a.out = out; a.img_rows = img_rows; a.cols = cols; a.ld = ld;
-  a.in_row0 = in_row0; a.in_rows = in_rows; a.out_row0 = out_row0; a.out_rows = out_rows;
-  a.radius = radius; a.nan_aware = nan_aware; a.nt = nt_rule<T>(img_rows, cols);
+  a.in = in; a.out = out;
+  set_band(a, img_rows, cols, ld, in_row0, in_rows, out_row0, out_rows);
+  a.radius = radius; a.nan_aware = nan_aware;
   return disk_filter(a, is_dilate != 0, impl, (hipStream_t)stream);
 }
 
@@ -176,9 +185,8 @@ int dilate_flag_api(const T* eroded, const T* last, T* opened, uint8_t* mask, ui
   if (!last || !mask) return smrf_fail(SMRF_E_ARG, "null last/mask pointer");
   DiskArgs<T> a{};
   a.in = eroded; a.out = opened; a.last = last; a.mask = mask; a.when = when; a.thr = thr; a.thr_lo = smrf_float_below(thr); a.widx = widx;
-  a.img_rows = img_rows; a.cols = cols; a.ld = ld;
-  a.in_row0 = in_row0; a.in_rows = in_rows; a.out_row0 = out_row0; a.out_rows = out_rows;
-  a.radius = radius; a.nan_aware = nan_aware; a.nt = nt_rule<T>(img_rows, cols); a.dense = dense;
+  set_band(a, img_rows, cols, ld, in_row0, in_rows, out_row0, out_rows);
+  a.radius = radius; a.nan_aware = nan_aware; a.dense = dense;
   return disk_filter(a, true, impl, (hipStream_t)stream);
 }
 
@@ -209,14 +217,12 @@ int open_flag_api(const T* last, T* opened, uint8_t* mask, uint8_t* when, double
     return smrf_fail(SMRF_E_UNSUPPORTED, "no fused opening kernel for radius %d at this dtype", radius);
   DiskArgs<T> a{};
   a.in = last; a.out = opened; a.mask = mask; a.when = when; a.thr = thr; a.thr_lo = smrf_float_below(thr); a.widx = widx;
-  a.img_rows = img_rows; a.cols = cols; a.ld = ld;
-  a.in_row0 = in_row0; a.in_rows = in_rows; a.out_row0 = out_row0; a.out_rows = out_rows;
+  set_band(a, img_rows, cols, ld, in_row0, in_rows, out_row0, out_rows);
   a.radius = 2 * radius;                               // the band check: `last` must reach 2r rows beyond the outputs
   if (int rc = check_band(a)) return rc;
   a.radius = radius;
   a.last = last + (long long)(out_row0 - in_row0) * ld; // the flag step compares against the same surface
   a.nan_aware = 0;
-  a.nt = nt_rule<T>(img_rows, cols);
   a.dense = mask ? dense : 0;
   a.seg = smrf_sw().ring_seg;
   return RingFn<T>::call(a, SMRF_RING_FUSED_OPEN, (hipStream_t)stream);
@@ -230,22 +236,20 @@ int chain_flag_api(const T* last, T* opened, uint8_t* mask, uint8_t* when, const
                    int out_rows, void* stream) {
   if (!last || !opened || !mask || !radii || !thr || !widx) return smrf_fail(SMRF_E_ARG, "null pointer");
   if (n < 1 || n > 4) return smrf_fail(SMRF_E_ARG, "a chain has 1..4 windows (got %d)", n);
-  const int pat = smrf_chain_match((int)sizeof(T), radii, n, 1ll << 62);
+  const int pat = smrf_chain_match((int)sizeof(T), radii, n, kPfAnySize);
   if (pat < 0 || smrf_chain_length(pat) != n)
     return smrf_fail(SMRF_E_UNSUPPORTED, "no chained launch for these %d radii at this dtype (smrf_pf_chain_length tells)", n);
   DiskArgs<T> b{};                                         // the band check: `last` must reach sum(2r) rows beyond the outputs
-  b.in = last; b.out = opened; b.img_rows = img_rows; b.cols = cols; b.ld = ld;
-  b.in_row0 = in_row0; b.in_rows = in_rows; b.out_row0 = out_row0; b.out_rows = out_rows;
+  b.in = last; b.out = opened;
+  set_band(b, img_rows, cols, ld, in_row0, in_rows, out_row0, out_rows);
   b.radius = smrf_chain_halo(pat);
   if (int rc = check_band(b)) return rc;
   if (b.radius >= img_rows) return smrf_fail(SMRF_E_UNSUPPORTED, "raster of %d rows is shorter than the chain's %d halo rows", img_rows, b.radius);
   ChainArgs<T> c{};
   c.in = last; c.out = opened; c.mask = mask; c.when = when;
   for (int k = 0; k < n; ++k) { c.thr[k] = thr[k]; c.widx[k] = widx[k]; }
-  c.img_rows = img_rows; c.cols = cols; c.ld = ld;
-  c.in_row0 = in_row0; c.in_rows = in_rows; c.out_row0 = out_row0; c.out_rows = out_rows;
+  set_band(c, img_rows, cols, ld, in_row0, in_rows, out_row0, out_rows);
   c.seg = smrf_sw().ring_seg;
-  c.nt = nt_rule<T>(img_rows, cols);
   c.dense0 = 0;
   if constexpr (sizeof(T) == 4) return smrf_chain_f32(pat, c, (hipStream_t)stream);
   else return smrf_chain_f64(pat, c, (hipStream_t)stream);
@@ -272,27 +276,37 @@ int progressive_filter_api(const T* Z, int rows, int cols, const int32_t* window
   T* P[3] = {E, E + plane, E + 2 * plane};
   int pe = 0, pl = -1;
   auto spare = [&]() { for (int k = 0; k < 3; ++k) if (k != pe && k != pl) return k; return 0; };
-  g_ero_inc_taken.assign((size_t)nwin, 0);
   // The first window's flag step writes every mask / when byte (DiskArgs::dense), so the planes are not cleared first:
   // one coalesced byte per cell instead of a memset pass plus scattered single-byte stores (window 0 flags the most cells)
   if (nwin == 0) {
     SMRF_HIP_CHECK(hipMemsetAsync(mask, 0, plane, stream));
     if (when) SMRF_HIP_CHECK(hipMemsetAsync(when, 0, plane, stream));
   }
-  // nan_aware < 0: the library finds out itself.  When the call starts with a chained / table-free launch, that launch
-  // carries the scan (it loads every cell of the raster; ChainArgs::nan_flag): it runs as if there were no NaN, the
-  // flag is read back after it (the one synchronising readback a separate count would need as well), and in the rare
-  // case it is set the call starts over on the NaN-aware two-pass kernels.  Otherwise: one count pass first.
-  const int fuse_mode0 = smrf_sw().fused;
-  const bool may_chain = nan_aware < 0 && nwin > 0 && fuse_mode0 != 0 && smrf_sw().chain != 0 &&
-                         smrf_sw().nan_ride != 0 &&   // 0: always a separate count pass (A/B runs)
-                         (impl == SMRF_IMPL_AUTO || impl == SMRF_IMPL_RING);
-  const int pat0 = may_chain ? smrf_chain_match((int)sizeof(T), windows, nwin, fuse_mode0 == 2 ? (1ll << 62) : (long long)plane) : -1;
-  // the flag of a speculative first launch: the first word of the workspace's E plane, which nothing touches before the
-  // first two-pass window's erosion (chained / fused launches never write plane pe = 0) - no allocation on this path
+  // Which launch every window takes is decided once, here, by smrf_pf_route (pf_route.h: small disks as one fused opening, runs
+  // of them as one chained launch, the large ones as two ring passes whose erosion may come from the previous window's); the
+  // loop below executes that plan.  route / pattern: one call-local buffer; the incremental-erosion flags are what
+  // smrf_pf_ero_inc_windows reports.
+  const SmrfSwitches& sw = smrf_sw();
+  SmrfPfRules rules{(int)sizeof(T), sw.fused, sw.chain, sw.ero_inc, impl, nan_aware > 0, 0};
+  std::vector<int32_t> plan_buf((size_t)2 * nwin);
+  int32_t* const route = plan_buf.data();
+  int32_t* const pattern = route + nwin;
+  g_ero_inc_taken.assign((size_t)nwin, 0);
+  auto make_plan = [&](int with_nan) {
+    rules.nan_aware = with_nan;
+    smrf_pf_route(rules, windows, nwin, rows, (long long)plane, route, g_ero_inc_taken.data(), pattern);
+  };
+  make_plan(nan_aware > 0);
+  // nan_aware < 0: the library finds out itself.  When the plan for a raster without NaN starts with a chained / table-free
+  // launch, that launch carries the scan (it loads every cell of the raster; ChainArgs::nan_flag): it runs as if there were no
+  // NaN, the flag is read back after it (the one synchronising readback a separate count would need as well), and in the rare
+  // case it is set the plan is made again for a raster with NaNs (scipy's NaN rule lives in the two-pass kernels only) and the
+  // call starts over.  Otherwise: one count pass first.  The flag is the first word of the workspace's E plane, which nothing
+  // touches before the first two-pass window's erosion (chained / fused launches never write plane pe = 0) - no allocation on
+  // this path.
   unsigned* d_nan = nullptr;
   if (nan_aware < 0) {
-    if (pat0 >= 0 && smrf_chain_halo(pat0) < rows) {
+    if (nwin > 0 && route[0] == SMRF_ROUTE_CHAIN && sw.nan_ride != 0) {   // SMRF_NAN_RIDE=0: always a separate count pass (A/B runs)
       d_nan = reinterpret_cast<unsigned*>(E);
       SMRF_HIP_CHECK(hipMemsetAsync(d_nan, 0, sizeof(unsigned), stream));
       nan_aware = 0;
@@ -300,6 +314,7 @@ int progressive_filter_api(const T* Z, int rows, int cols, const int32_t* window
       int64_t c = 0;
       if (int rc = count_nan_api<T>(Z, (int64_t)plane, &c, stream_)) return rc;
       nan_aware = c > 0;
+      if (nan_aware) make_plan(1);
     }
   }
   // measurement form (smrf_progressive_filter_timed_*): an event on the stream at every window boundary
@@ -313,8 +328,8 @@ int progressive_filter_api(const T* Z, int rows, int cols, const int32_t* window
     for (auto& e : ev) SMRF_HIP_CHECK(hipEventCreate(&e));
     SMRF_HIP_CHECK(hipEventRecord(ev[0], stream));
   }
-  auto window_done = [&](int i, int route) -> int {
-    if (h_window_route) h_window_route[i] = route;
+  auto window_done = [&](int i) -> int {
+    if (h_window_route) h_window_route[i] = route[i];
     if (h_window_ms) SMRF_HIP_CHECK(hipEventRecord(ev[(size_t)i + 1], stream));
     return SMRF_OK;
   };
@@ -326,107 +341,74 @@ int progressive_filter_api(const T* Z, int rows, int cols, const int32_t* window
     return SMRF_OK;
   };
   const T* last = Z;
-  // small disks: opening + flag in ONE launch, the eroded surface never leaves the CU (morph_fused.h; 10 instead of
-  // 22 B/cell in fp32), and runs of consecutive small windows (chain.hip's patterns: 1, 2, 3 | 1, 2 | 2, 3 | 4, 5, and the
-  // table-free single launches 4..10) as ONE launch that only reads the first window's input and writes the last window's
-  // opening (morph_chain.h).  Not for rasters with NaNs (scipy's NaN rule lives in the two-pass kernels only) - except that
-  // the FIRST launch of a call with nan_aware < 0 runs speculatively and carries the NaN scan: if it meets a NaN its
-  // results are discarded and the call starts over on the two-pass kernels (below).
-  // SMRF_FUSED: 0 = never, 1 = default rule, 2 = every radius that has a fused kernel whatever the raster size (tests);
-  // SMRF_CHAIN: 0 = no chains (every window its own launch).
-  const int fuse_mode = smrf_sw().fused;
-  const bool fuse_ok0 = (impl == SMRF_IMPL_AUTO || impl == SMRF_IMPL_RING) && fuse_mode != 0;
-  const bool chain_ok0 = smrf_sw().chain != 0;
-  // window R's erosion from window R-1's (morph_incero.h): e_R = min(erode(e_{R-1}, cross), min over the
-  // leftover cells P_R of last).  For window i when the raster has no NaN (scipy's NaN rule lives in the ring kernels), impl is
-  // auto or ring, windows[i] = windows[i-1] + 1, window i-1 ran as two ring passes (its eroded plane is still in the
-  // workspace) and an instance exists for the radius; SMRF_ERO_INC: 0 = never, 1 = where the measured table says it wins,
-  // 2 = every such window.  The identity holds on any raster size (tests/test_ero_inc.py), so there is no size condition.
-  const int inc_mode = smrf_sw().ero_inc;
-  int ring_two_pass_at = -2;                             // the latest window that ran as two ring passes
   for (int i = 0; i < nwin;) {
     const int r = windows[i];
     const int po = spare();
     T* opened = P[po];
-    const bool fuse_ok = !nan_aware && fuse_ok0;           // (nan_aware can change once: a speculative first launch that met a NaN)
-    const bool chain_ok = fuse_ok && chain_ok0;
-    const int pat = chain_ok ? smrf_chain_match((int)sizeof(T), windows + i, nwin - i, fuse_mode == 2 ? (1ll << 62) : (long long)plane) : -1;
-    // a speculative first launch was decided on pat0 above: the loop must take exactly that launch, or a NaN raster would
-    // run the NaN-free kernels unscanned
-    if (i == 0 && d_nan && pat != pat0) return smrf_fail(SMRF_E_HIP, "internal: first launch %d is not the one the NaN scan rides in (%d)", pat, pat0);
-    if (pat >= 0 && smrf_chain_halo(pat) < rows) {
-      const int len = smrf_chain_length(pat);
-      ChainArgs<T> c{};
-      c.in = last; c.out = opened; c.mask = mask; c.when = when;
-      for (int k = 0; k < len; ++k) { c.thr[k] = thr[i + k]; c.widx[k] = i + k; }
-      c.img_rows = rows; c.cols = cols; c.ld = cols;
-      c.in_row0 = 0; c.in_rows = rows; c.out_row0 = 0; c.out_rows = rows;
-      c.seg = smrf_sw().ring_seg;
-      c.nt = nt_rule<T>(rows, cols);
-      c.dense0 = i == 0;
-      c.nan_flag = i == 0 ? d_nan : nullptr;
-      int crc;
-      if constexpr (sizeof(T) == 4) crc = smrf_chain_f32(pat, c, stream);
-      else crc = smrf_chain_f64(pat, c, stream);
-      if (crc) return crc;
-      if (i == 0 && d_nan) {                               // the speculative first launch: did it meet a NaN?
-        unsigned h = 0;
-        SMRF_HIP_CHECK(hipMemcpyAsync(&h, d_nan, sizeof(h), hipMemcpyDeviceToHost, stream));
-        SMRF_HIP_CHECK(hipStreamSynchronize(stream));
-        d_nan = nullptr;
-        if (h) {                                           // start over with scipy's NaN rule (two-pass kernels only)
-          nan_aware = 1;
-          pe = 0; pl = -1;
-          last = Z;
-          continue;                                        // i is still 0
+    switch (route[i]) {
+      case SMRF_ROUTE_CHAIN: {   // windows i .. i + len - 1 in ONE launch that reads `last` and writes the last window's opening (morph_chain.h)
+        const int len = smrf_chain_length(pattern[i]);
+        ChainArgs<T> c{};
+        c.in = last; c.out = opened; c.mask = mask; c.when = when;
+        for (int k = 0; k < len; ++k) { c.thr[k] = thr[i + k]; c.widx[k] = i + k; }
+        set_band(c, rows, cols, cols, 0, rows, 0, rows);
+        c.seg = sw.ring_seg;
+        c.dense0 = i == 0;
+        c.nan_flag = d_nan;                                  // not NULL: the speculative first launch
+        int crc;
+        if constexpr (sizeof(T) == 4) crc = smrf_chain_f32(pattern[i], c, stream);
+        else crc = smrf_chain_f64(pattern[i], c, stream);
+        if (crc) return crc;
+        if (d_nan) {                                         // did it meet a NaN?
+          unsigned h = 0;
+          SMRF_HIP_CHECK(hipMemcpyAsync(&h, d_nan, sizeof(h), hipMemcpyDeviceToHost, stream));
+          SMRF_HIP_CHECK(hipStreamSynchronize(stream));
+          d_nan = nullptr;
+          if (h) {                                           // its results are discarded: start over with scipy's NaN rule
+            nan_aware = 1;
+            make_plan(1);
+            continue;                                        // i is still 0, the planes' roles and `last` as at the start
+          }
         }
+        if (nwin > 1) { last = opened; pl = po; }
+        for (int k = 0; k < len; ++k)                        // the chain's time lands on its first window, the others read ~0
+          if (int rc = window_done(i + k)) return rc;
+        i += len;
+        break;
       }
-      if (nwin > 1) { last = opened; pl = po; }
-      for (int k = 0; k < len; ++k)                        // the chain's time lands on its first window, the others read ~0
-        if (int rc = window_done(i + k, SMRF_ROUTE_CHAIN + k)) return rc;
-      i += len;
-      continue;
+      case SMRF_ROUTE_FUSED:     // opening + flag in ONE launch, the eroded surface never leaves the CU (morph_fused.h; 10 instead of 22 B/cell in fp32)
+        if (int rc = open_flag_api<T>(last, opened, mask, when, thr[i], i, rows, cols, cols, 0, rows, 0, rows, r, stream_, i == 0)) return rc;
+        if (nwin > 1) { last = opened; pl = po; }
+        if (int rc = window_done(i)) return rc;
+        ++i;
+        break;
+      default:                   // two passes: ring or direct kernels by `impl`, the copy kernel for radius 0
+        if (g_ero_inc_taken[(size_t)i]) {
+          // window R's erosion from window R-1's (morph_incero.h): e_R = min(erode(e_{R-1}, cross), min over the
+          // leftover cells P_R of last).  e_R goes into the spare plane (it held opened_{R-2}), then opened_R goes over e_{R-1}
+          if constexpr (sizeof(T) == 4) {
+            if (int rc = smrf_inc_erode_f32(P[pe], last, P[po], rows, cols, cols, r, nt_rule<T>(rows, cols), stream)) return rc;
+          } else {
+            return smrf_fail(SMRF_E_HIP, "internal: no incremental erosion at this dtype");
+          }
+          opened = P[pe];
+          if (int rc = dilate_flag_api<T>(P[po], last, opened, mask, when, thr[i], i, rows, cols, cols, 0, rows, 0, rows, r,
+                                          nan_aware, impl, stream_, 0))
+            return rc;
+          last = opened;
+          pl = pe;
+          pe = po;
+        } else {
+          if (int rc = disk_filter_api<T>(last, P[pe], rows, cols, cols, 0, rows, 0, rows, r, 0, nan_aware, impl, stream_)) return rc;
+          if (int rc = dilate_flag_api<T>(P[pe], last, opened, mask, when, thr[i], i, rows, cols, cols, 0, rows, 0, rows, r,
+                                          nan_aware, impl, stream_, i == 0))
+            return rc;
+          if (nwin > 1) { last = opened; pl = po; }           // neilpy.py:1675-1676
+        }
+        if (int rc = window_done(i)) return rc;
+        ++i;
+        break;
     }
-    // above R = 8 the fused kernel's 4R warm-up rows per segment only pay on rasters large enough for long segments
-    // (4096^2, windows 1..18: 1.64 ms with R <= 8 fused, 1.70 ms with 10..14 as well; 8192^2: 5.9 -> 5.2 ms with them);
-    // round 5, after the launches' segmentation changed: from 20 Mi cells (5000^2: R = 11..13 -7 ... -11 %, 6000^2 -10 ... -17 %,
-    // R = 14 equal; 4096^2 and below +3 ... +20 %: profiles/r05_logs/segments/min_cells_fused.log); 48 Mi until then
-    if (fuse_ok && smrf_fused_radius((int)sizeof(T), r) && (r <= 8 || fuse_mode == 2 || plane >= ((size_t)20 << 20))) {
-      if (int rc = open_flag_api<T>(last, opened, mask, when, thr[i], i, rows, cols, cols, 0, rows, 0, rows, r, stream_, i == 0)) return rc;
-      if (nwin > 1) { last = opened; pl = po; }
-      if (int rc = window_done(i, SMRF_ROUTE_FUSED)) return rc;
-      ++i;
-      continue;
-    }
-    const int eff = impl == SMRF_IMPL_AUTO ? (r <= SMRF_RING_MAX_RADIUS ? SMRF_IMPL_RING : SMRF_IMPL_DIRECT) : impl;
-    const bool inc = inc_mode != 0 && !nan_aware && eff == SMRF_IMPL_RING && i > 0 && ring_two_pass_at == i - 1 && pl >= 0 &&
-                     r == windows[i - 1] + 1 && smrf_inc_erode_has((int)sizeof(T), r) &&
-                     (inc_mode == 2 || smrf_inc_erode_adopted((int)sizeof(T), r));
-    if (inc) {
-      // e_R goes into the spare plane (it held opened_{R-2}), then opened_R goes over e_{R-1}
-      if constexpr (sizeof(T) == 4) {
-        if (int rc = smrf_inc_erode_f32(P[pe], last, P[po], rows, cols, cols, r, nt_rule<T>(rows, cols), stream)) return rc;
-      } else {
-        return smrf_fail(SMRF_E_HIP, "internal: no incremental erosion at this dtype");
-      }
-      opened = P[pe];
-      if (int rc = dilate_flag_api<T>(P[po], last, opened, mask, when, thr[i], i, rows, cols, cols, 0, rows, 0, rows, r,
-                                      nan_aware, impl, stream_, 0))
-        return rc;
-      last = opened;
-      pl = pe;
-      pe = po;
-      g_ero_inc_taken[(size_t)i] = 1;
-    } else {
-      if (int rc = disk_filter_api<T>(last, P[pe], rows, cols, cols, 0, rows, 0, rows, r, 0, nan_aware, impl, stream_)) return rc;
-      if (int rc = dilate_flag_api<T>(P[pe], last, opened, mask, when, thr[i], i, rows, cols, cols, 0, rows, 0, rows, r,
-                                      nan_aware, impl, stream_, i == 0))
-        return rc;
-      if (nwin > 1) { last = opened; pl = po; }           // neilpy.py:1675-1676
-    }
-    if (eff == SMRF_IMPL_RING && r >= 1) ring_two_pass_at = i;
-    if (int rc = window_done(i, r == 0 ? SMRF_ROUTE_COPY : eff == SMRF_IMPL_RING ? SMRF_ROUTE_TWO_PASS : SMRF_ROUTE_DIRECT)) return rc;
-    ++i;
   }
   return finish();
 }
@@ -484,8 +466,20 @@ int smrf_pf_chain_length(int elem_size, const int32_t* h_radii, int n, int64_t r
   // SMRF_FUSED=0 = no chained / table-free launches, SMRF_FUSED=2 = every pattern whatever the raster size
   const SmrfSwitches& sw = smrf_sw();
   if (sw.chain == 0 || sw.fused == 0) return 0;
-  const int pat = smrf_chain_match(elem_size, h_radii, n, sw.fused == 2 ? (1ll << 62) : (long long)raster_cells);
+  const int pat = smrf_chain_match(elem_size, h_radii, n, sw.fused == 2 ? kPfAnySize : (long long)raster_cells);
   return pat < 0 ? 0 : smrf_chain_length(pat);
+}
+int smrf_pf_plan(int elem_size, const int32_t* h_windows, int n, int rows, int64_t cells, int nan_aware, int impl, int band,
+                 int32_t* h_route, uint8_t* h_ero_inc) {
+  if (n < 0 || (n > 0 && (!h_windows || !h_route || !h_ero_inc))) return smrf_fail(SMRF_E_ARG, "null pointer");
+  if ((elem_size != 4 && elem_size != 8) || rows < 1 || cells < 0 || band < 0 || band > 2)
+    return smrf_fail(SMRF_E_ARG, "bad plan question (element size %d, %d rows, band %d)", elem_size, rows, band);
+  for (int i = 0; i < n; ++i)
+    if (h_windows[i] < 0) return smrf_fail(SMRF_E_ARG, "negative window %d", h_windows[i]);
+  const SmrfSwitches& sw = smrf_sw();
+  smrf_pf_route(SmrfPfRules{elem_size, sw.fused, sw.chain, sw.ero_inc, impl, nan_aware != 0, band}, h_windows, n, rows,
+                (long long)cells, h_route, h_ero_inc);
+  return SMRF_OK;
 }
 int smrf_pf_chain_flag_f32(const float* d_last, float* d_opened, uint8_t* d_mask, uint8_t* d_when_dropped,
                            const int32_t* h_radii, const double* h_thresholds, const int32_t* h_window_index, int n_windows,

@@ -48,14 +48,11 @@ struct ChainArgs {
   unsigned* nan_flag; // if not NULL: set to 1 when any input cell this launch loads is NaN (it loads every cell of the band)
 };
 
-// chain dispatch (chain.hip): the pattern a window list starts with (-1: none), its length and halo rows, the launch
-SMRF_HIDDEN int smrf_chain_match(int elem_size, const int32_t* windows, int n, long long cells);
-SMRF_HIDDEN int smrf_chain_length(int pattern);
-SMRF_HIDDEN int smrf_chain_halo(int pattern);
+// chain dispatch (chain.hip): the launch of pattern `pattern` of pf_route.h's kPatterns (smrf_chain_match finds it for a window list)
 SMRF_HIDDEN int smrf_chain_f32(int pattern, const ChainArgs<float>& a, hipStream_t s);
 SMRF_HIDDEN int smrf_chain_f64(int pattern, const ChainArgs<double>& a, hipStream_t s);
 
-// row pairs per batch of a chain kernel, per dtype and pattern index of chain.hip (tuning builds: -DSMRF_CHAIN_NP_ALL=n)
+// row pairs per batch of a chain kernel, per dtype and pattern index of pf_route.h (tuning builds: -DSMRF_CHAIN_NP_ALL=n)
 #ifndef SMRF_CHAIN_NP_ALL
 #define SMRF_CHAIN_NP_ALL 0
 #endif
@@ -97,7 +94,7 @@ struct ChainCfg {
 // pair are 4R registers in fp32 and 8R in fp64 when taken at once - what made every fp64 single-window form spill.  In groups
 // of G cells per side, the next group in flight while this one is folded into the growing window, they are 8G (16G)
 // registers whatever R: the fp64 singles of chain.hip (R = 4, 5, 7, 8; 112-160 registers).  The same form for fp32
-// R = 11..14 was built and measured 12-16 % slower than the fused kernels (chain.hip): tuning builds only.
+// R = 11..14 was built and measured 12-16 % slower than the fused kernels (pf_route.h): tuning builds only.
 #ifndef SMRF_CHAIN_GROUP
 #define SMRF_CHAIN_GROUP(T, R) chain_group<T>(R)
 #endif

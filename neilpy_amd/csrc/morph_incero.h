@@ -26,10 +26,7 @@
 namespace smrf {
 
 #include "ero_inc.inc"
-#include "ero_inc_adopt.inc"
-
-#define SMRF_INCERO_MIN_RADIUS 16   // the first window after the first two-pass window of a default call (15)
-#define SMRF_INCERO_MAX_RADIUS 64
+// (SMRF_INCERO_MIN_RADIUS / _MAX_RADIUS, the radii with an instance, and the adoption table ero_inc_adopt.inc: pf_route.h)
 
 // Two choices per radius, both made by measurement on MI355X at 16384^2 (profiles/incero_mirror.md sections 1 and 3):
 //   kIncEroPlanKind  how a batch's LDS reads are planned (IncEroCfg::make_plan).  The mirror plan with split groups everywhere;

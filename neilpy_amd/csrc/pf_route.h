@@ -1,0 +1,174 @@
+// Which launch every window of progressive_filter takes: the whole rule, as tables and one pure function (smrf_pf_route).
+// The whole-raster driver (morph.hip, progressive_filter_api) executes the plan this function makes, and the row-band driver
+// (neilpy_amd/sharded.py) asks the same function through smrf_pf_plan of the C ABI.  Plain C++, no HIP: included by
+// smrf_common.h and compiled on its own by tests/test_pf_route_host.py.
+#pragma once
+#include <cstdint>
+
+// The values of include/smrf_hip.h the rule speaks in (SMRF_IMPL_*, SMRF_RING_MAX_RADIUS, SMRF_ROUTE_*), restated so that the
+// header compiles without it and checked wherever both are seen.
+constexpr int kPfImplAuto = 0, kPfImplRing = 1, kPfImplDirect = 2, kPfRingMaxRadius = 64;
+constexpr int kPfRouteTwoPass = 0, kPfRouteFused = 1, kPfRouteDirect = 2, kPfRouteCopy = 3, kPfRouteChain = 4;
+#ifdef SMRF_HIP_H
+static_assert(kPfImplAuto == SMRF_IMPL_AUTO && kPfImplRing == SMRF_IMPL_RING && kPfImplDirect == SMRF_IMPL_DIRECT &&
+              kPfRingMaxRadius == SMRF_RING_MAX_RADIUS && kPfRouteTwoPass == SMRF_ROUTE_TWO_PASS &&
+              kPfRouteFused == SMRF_ROUTE_FUSED && kPfRouteDirect == SMRF_ROUTE_DIRECT && kPfRouteCopy == SMRF_ROUTE_COPY &&
+              kPfRouteChain == SMRF_ROUTE_CHAIN, "pf_route.h restates include/smrf_hip.h");
+#endif
+
+// ------------------------------------------------------------------------------------------
+// chained / table-free launches (morph_chain.h; chain.hip instantiates one kernel per pattern index)
+// ------------------------------------------------------------------------------------------
+struct SmrfChainPattern { int n; int r[4]; long long min_cells; long long min_cells_f64; };   // min_cells < 0: no kernel at that dtype
+// The launches that exist, in the order they are tried (NP row pairs per batch - SMRF_CHAIN_NP - and the occupancy a kernel
+// is built for are per pattern, chain.hip).  A single window is a chain of one: the same table-free stages, which up to
+// R = 10 beat the table-building fused kernel of morph_fused.h (and the two ring passes of R = 9): at R <= 6 they run at the
+// device's copy rate (0.55 ms for the 10 B/cell of a 16384^2 fp32 window).  min_cells: the smallest raster a pattern is
+// taken for (a chain's segments start sum(2R) rows early and its strips lose sum(2R) columns per side).
+// Measured on 16384^2 fp32 against round 2's one fused launch (two ring passes at R = 9) per window, ms
+// (profiles/r03_chain_windows.md): 1, 2, 3: 0.79 against 1.96; 4, 5: 0.84 against 1.42 (on 4096^2 two single launches
+// win: 0.103 against 0.114); 6: 0.55 against 0.76; 7: 0.67 against 0.79; 8: 0.65 against 0.84; 9: 0.72 against 1.07;
+// 10: 0.79 against 0.99; a chain 6, 7 takes 1.31 (two singles 1.22; round 4, built for 3 waves per SIMD - 154-158 registers,
+// no scratch: 1.28 against 1.18, profiles/r04_logs/chain_6_7_ab.log), a chain 8, 9 (172 registers, two workgroups per CU)
+// 3.1 against 2.0: neither exists.
+// Round 4 (grouped neighbour reads, chain_stage_grouped; profiles/r04_chain_grouped.md): fp64 singles exist at R = 4, 5, 7, 8
+// (8192^2: 0.279 against the fused opening's 0.374 ms at R = 4, 0.308 / 0.330 at 5, 0.425 against two ring passes' 0.549 at 7,
+// 0.461 / 0.531 at 8; R = 6 loses to the fused kernel by 7 %, R = 9, 10 - 174-186 registers, two waves per SIMD - to the ring
+// passes by 14-20 %; on 4096^2 only R = 4 and 7 still win).  The fp32 singles R = 11..14 in the grouped form (139-166
+// registers, 3 waves per SIMD) measured 12-16 % SLOWER than the fused kernels (0.99 / 1.01 / 1.08 / 1.14 against 0.85 / 0.89 /
+// 0.96 / 1.02 ms on 16384^2): the cell-by-cell window growth costs R min / max per row and stage where the table costs
+// K - 1 + ~3, and from R = 11 that outweighs the table's two extra barriers.  They do not exist.
+// The fp64 chain 1, 2, 3 (134 registers at one row pair per batch, 3 waves per SIMD): 0.578 against 0.615 ms for chain 1, 2 + the
+// fused R = 3 on 8192^2, slower on 4096^2 and 1024^2 (profiles/r04_logs/chain_123_f64_ab.log): from 48 Mi cells in round 4.
+// Round 5: the thresholds below were measured again after the launches' segmentation changed (seg_rule.h: one round cut by the
+// cost model on rasters this small; profiles/r05_logs/segments/min_cells_f32.log, min_cells_f64.log: default routing against
+// every kind that exists on 1024^2 ... 6000^2).  fp32: the chain 4, 5 wins from 5000^2 (-6 %, 6000^2 -11 %; loses 7-19 % on
+// 2048^2 and 4096^2), the singles R = 9, 10 win 17-27 % on 5000^2 and 6000^2; R = 9 also wins 9-13 % on 1024^2 ... 3000^2 and ties
+// on 4096^2 (any size now), R = 10 ties below 5000^2.  fp64: the chain
+// 1, 2, 3 and the single R = 5 win on every raster tried (-4 ... -16 %), R = 7 from 2048^2 (-7 %), R = 8 from 4096^2
+// (-11 ... -21 %; +10 ... +14 % below).
+constexpr long long kLarge = 20ll << 20;
+constexpr long long kMid = 16ll << 20;
+constexpr long long kSmall = 4ll << 20;
+constexpr long long kNever = -1;
+constexpr SmrfChainPattern kPatterns[] = {{3, {1, 2, 3, 0}, 0, 0}, {2, {1, 2, 0, 0}, 0, 0}, {2, {2, 3, 0, 0}, 0, 0}, {2, {4, 5, 0, 0}, kLarge, kNever},
+                                          {1, {4, 0, 0, 0}, 0, 0}, {1, {5, 0, 0, 0}, 0, 0}, {1, {6, 0, 0, 0}, 0, kNever}, {1, {7, 0, 0, 0}, 0, kSmall},
+                                          {1, {8, 0, 0, 0}, 0, kMid}, {1, {9, 0, 0, 0}, 0, kNever}, {1, {10, 0, 0, 0}, kLarge, kNever}};
+constexpr int kNPatterns = (int)(sizeof(kPatterns) / sizeof(kPatterns[0]));
+constexpr long long kPfAnySize = 1ll << 62;   // `cells` of a question that no size threshold is to answer
+
+// the pattern a window list starts with on a raster of `cells` cells (-1: none), its length and its halo rows sum(2R)
+inline int smrf_chain_match(int elem_size, const int32_t* windows, int n, long long cells) {
+  for (int p = 0; p < kNPatterns; ++p) {
+    const long long mc = elem_size == 8 ? kPatterns[p].min_cells_f64 : kPatterns[p].min_cells;
+    if (kPatterns[p].n > n || mc < 0 || cells < mc) continue;
+    bool ok = true;
+    for (int i = 0; i < kPatterns[p].n; ++i) ok = ok && windows[i] == kPatterns[p].r[i];
+    if (ok) return p;
+  }
+  return -1;
+}
+inline int smrf_chain_length(int pat) { return pat >= 0 && pat < kNPatterns ? kPatterns[pat].n : 0; }
+inline int smrf_chain_halo(int pat) {
+  int s = 0;
+  if (pat >= 0 && pat < kNPatterns)
+    for (int i = 0; i < kPatterns[pat].n; ++i) s += 2 * kPatterns[pat].r[i];
+  return s;
+}
+
+// ------------------------------------------------------------------------------------------
+// fused opening + flag (morph_fused.h)
+// ------------------------------------------------------------------------------------------
+// radii whose progressive_filter window runs as ONE fused opening + flag launch, per dtype: measured
+// against the two ring passes per radius on the 16384^2 benchmark DEM (gpurun_out/r02/fused3_per_radius_f32.log,
+// fused2_per_radius_f64.log, fused_hi_f32.log).  fp32: 1..8 and 10..14 (9 loses by 3 %, 15 and up by 20 % and more);
+// fp64, whose tables are twice as large: 1..6.
+#ifndef SMRF_FUSED_MAX_RADIUS
+#define SMRF_FUSED_MAX_RADIUS 14
+#endif
+constexpr bool smrf_fused_radius(int elem_size, int r) {
+  if (r < 1 || r > SMRF_FUSED_MAX_RADIUS) return false;
+  return elem_size == 4 ? (r != 9) : (r <= 6);
+}
+// above R = 8 the fused kernel's 4R warm-up rows per segment only pay on rasters large enough for long segments
+// (4096^2, windows 1..18: 1.64 ms with R <= 8 fused, 1.70 ms with 10..14 as well; 8192^2: 5.9 -> 5.2 ms with them);
+// round 5, after the launches' segmentation changed: from 20 Mi cells (5000^2: R = 11..13 -7 ... -11 %, 6000^2 -10 ... -17 %,
+// R = 14 equal; 4096^2 and below +3 ... +20 %: profiles/r05_logs/segments/min_cells_fused.log); 48 Mi until then.
+// A row band takes the fused opening up to kFusedSmallRadius only, whatever its size: a band's segments are short against
+// the 4R warm-up rows (tools/band_compute.py).
+constexpr int kFusedSmallRadius = 8;
+constexpr long long kFusedLargeCells = 20ll << 20;
+
+// ------------------------------------------------------------------------------------------
+// incremental erosion (morph_incero.h; incero.hip instantiates one kernel per radius)
+// ------------------------------------------------------------------------------------------
+#define SMRF_INCERO_MIN_RADIUS 16   // the first window after the first two-pass window of a default call (15)
+#define SMRF_INCERO_MAX_RADIUS 64
+namespace smrf {
+#include "ero_inc_adopt.inc"
+}  // namespace smrf
+// has = an instance exists for this dtype and radius, adopted = the measured per-radius table takes it
+inline bool smrf_inc_erode_has(int elem_size, int radius) {
+  return elem_size == 4 && radius >= SMRF_INCERO_MIN_RADIUS && radius <= SMRF_INCERO_MAX_RADIUS;
+}
+inline bool smrf_inc_erode_adopted(int elem_size, int radius) {
+  return smrf_inc_erode_has(elem_size, radius) && smrf::kEroIncAdoptF32[radius] != 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// the plan
+// ------------------------------------------------------------------------------------------
+struct SmrfPfRules {
+  int elem_size;   // 4 or 8
+  int fused;       // SMRF_FUSED: 0 = never a fused / chained launch, 1 = by the size rules, 2 = every one that exists whatever the size (tests)
+  int chain;       // SMRF_CHAIN: 0 = no chained / table-free launches (every window its own launch)
+  int ero_inc;     // SMRF_ERO_INC: 0 = never, 1 = where ero_inc_adopt.inc says it wins, 2 = every eligible window
+  int impl;        // SMRF_IMPL_*: the fused, chained and incremental kernels are ring kernels (auto or ring only)
+  int nan_aware;   // != 0: the raster may hold NaNs.  scipy's NaN rule lives in the two-pass kernels only
+  int band;        // 0 = a whole raster; 1 = the row-band driver: `rows` is the image's rows, `cells` what one launch marches (the
+                   // longest band with its two-sided margin), fused openings up to kFusedSmallRadius only, and no incremental erosion
+                   // (its kernel takes whole rasters: a band's e_{R-1} margin rows are stale after a halo exchange);
+                   // 2 = a row band whose launches cannot be chained either (the edge-first split of overlap=True, a single band)
+};
+
+// Window by window, for i = 0 .. n - 1 (windows[i] >= 0):
+//   route[i]    SMRF_ROUTE_*.  A chained launch takes the windows i .. i + len - 1, which read SMRF_ROUTE_CHAIN + position.
+//   ero_inc[i]  1 = the window's erosion comes from the previous window's (inc_erode_kernel); only beside SMRF_ROUTE_TWO_PASS
+//   pattern[i]  (may be NULL) at the head of a chained launch its index in kPatterns, -1 everywhere else
+// chain: no NaN, impl auto or ring, SMRF_FUSED and SMRF_CHAIN on, a pattern matches the windows from i on at this size, and the
+// raster has more rows than the pattern's halo; else fused: the first three again, a fused kernel for the radius, and the
+// radius small or the (whole) raster large; else copy for radius 0, two ring passes up to kPfRingMaxRadius under auto, the
+// direct kernel beyond.  Incremental erosion: a whole raster without NaN, this window and the one before both two ring passes,
+// radius = the previous radius + 1, an instance exists, and the table adopts it or SMRF_ERO_INC = 2.  The identity holds on
+// any raster size (tests/test_ero_inc.py), so there is no size condition.
+inline void smrf_pf_route(const SmrfPfRules& k, const int32_t* windows, int n, int rows, long long cells, int32_t* route,
+                          uint8_t* ero_inc, int32_t* pattern = nullptr) {
+  const bool fuse_ok = !k.nan_aware && (k.impl == kPfImplAuto || k.impl == kPfImplRing) && k.fused != 0;
+  const bool chain_ok = fuse_ok && k.chain != 0 && k.band != 2;
+  for (int i = 0; i < n; ++i) {
+    ero_inc[i] = 0;
+    if (pattern) pattern[i] = -1;
+  }
+  for (int i = 0; i < n;) {
+    const int r = windows[i];
+    const int pat = chain_ok ? smrf_chain_match(k.elem_size, windows + i, n - i, k.fused == 2 ? kPfAnySize : cells) : -1;
+    const int len = pat >= 0 && smrf_chain_halo(pat) < rows ? smrf_chain_length(pat) : 0;
+    if (len) {
+      if (pattern) pattern[i] = pat;
+      for (int j = 0; j < len; ++j) route[i + j] = kPfRouteChain + j;
+      i += len;
+      continue;
+    }
+    if (fuse_ok && smrf_fused_radius(k.elem_size, r) &&
+        (r <= kFusedSmallRadius || (!k.band && (k.fused == 2 || cells >= kFusedLargeCells)))) {
+      route[i++] = kPfRouteFused;
+      continue;
+    }
+    const int eff = k.impl == kPfImplAuto ? (r <= kPfRingMaxRadius ? kPfImplRing : kPfImplDirect) : k.impl;
+    route[i] = r == 0 ? kPfRouteCopy : eff == kPfImplRing ? kPfRouteTwoPass : kPfRouteDirect;
+    ero_inc[i] = !k.band && k.ero_inc != 0 && !k.nan_aware && i > 0 && route[i] == kPfRouteTwoPass &&
+                 route[i - 1] == kPfRouteTwoPass && r == windows[i - 1] + 1 && smrf_inc_erode_has(k.elem_size, r) &&
+                 (k.ero_inc == 2 || smrf_inc_erode_adopted(k.elem_size, r));
+    ++i;
+  }
+}

@@ -105,6 +105,8 @@ inline float smrf_float_below(double t) {
 }
 
 #include "seg_rule.h"   // smrf_seg_len, smrf_ring_plan: how a launch is cut into row segments (plain C++: tests/test_host_logic.py compiles it)
+#include "pf_route.h"   // smrf_pf_route: which launch every progressive_filter window takes, with smrf_fused_radius, the chain patterns and
+                        // the incremental erosion's radii (plain C++: tests/test_pf_route_host.py compiles it)
 
 // Workgroups of `Kern` (`block` threads, `lds` bytes of dynamic LDS) one CU really holds (registers + LDS), asked once per
 // kernel and device - the attribute that allows more than 48 KB of dynamic LDS is per device too - and at least 1.
@@ -158,21 +160,8 @@ struct DiskArgs {
 // ring-kernel dispatchers, one per (dtype, radius % SMRF_RING_PARTS); defined in ring_part.hip.
 // mode: erosion, dilation (+ flag step when mask != NULL), or the fused opening + flag of morph_fused.h (in = last)
 enum { SMRF_RING_ERODE = 0, SMRF_RING_DILATE = 1, SMRF_RING_FUSED_OPEN = 2 };
-// radii whose progressive_filter window runs as ONE fused opening + flag launch (morph_fused.h), per dtype: measured
-// against the two ring passes per radius on the 16384^2 benchmark DEM (gpurun_out/r02/fused3_per_radius_f32.log,
-// fused2_per_radius_f64.log, fused_hi_f32.log).  fp32: 1..8 and 10..14 (9 loses by 3 %, 15 and up by 20 % and more);
-// fp64, whose tables are twice as large: 1..6.
-#ifndef SMRF_FUSED_MAX_RADIUS
-#define SMRF_FUSED_MAX_RADIUS 14
-#endif
-constexpr bool smrf_fused_radius(int elem_size, int r) {
-  if (r < 1 || r > SMRF_FUSED_MAX_RADIUS) return false;
-  return elem_size == 4 ? (r != 9) : (r <= 6);
-}
-// incremental erosion of progressive_filter's consecutive windows (morph_incero.h, defined in incero.hip): has = an instance
-// exists for this dtype and radius, adopted = the measured per-radius table takes it (csrc/ero_inc_adopt.inc)
-SMRF_HIDDEN bool smrf_inc_erode_has(int elem_size, int radius);
-SMRF_HIDDEN bool smrf_inc_erode_adopted(int elem_size, int radius);
+// incremental erosion of progressive_filter's consecutive windows (morph_incero.h, defined in incero.hip); which radii have an
+// instance and which the default routing adopts: pf_route.h
 SMRF_HIDDEN int smrf_inc_erode_f32(const float* e_prev, const float* last, float* out, int rows, int cols, long long ld,
                                    int radius, int nt, hipStream_t s);
 #define SMRF_RING_PARTS 8

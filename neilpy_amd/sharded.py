@@ -54,20 +54,24 @@ class HipBandOps:
         _lib.check(fn(_ptr(band), band.numel(), C.byref(cnt), _stream()))
         return cnt.value > 0
 
-    def can_fuse(self, t, radius):
-        """a window of this radius can run as one fused opening + flag launch on a band (csrc/morph_fused.h).  Only the
-        radii whose 4r warm-up rows are short against a band's segments: r <= 8."""
+    def head_launch(self, t, radii, img_rows, cells, chain=True):
+        """(route, n): the launch the library's routing rule (csrc/pf_route.h, asked through smrf_pf_plan with band = 1 and this
+        object's impl) takes for the window at the head of ``radii`` on a NaN-free row band, and how many of those windows it
+        covers: ``ROUTE_CHAIN`` with the n windows one chained / table-free launch opens (:meth:`chain_flag`),
+        ``ROUTE_FUSED`` (:meth:`open_flag`), or any other route for the two passes; n = 1 for both.  ``cells``: the cells such
+        a launch marches; ``chain=False``: a band whose launches cannot be chained.  The library applies its own SMRF_FUSED
+        / SMRF_CHAIN switches, the ones smrf_progressive_filter_* routes by."""
         import torch
-        return 1 <= radius <= 8 and bool(self.lib.smrf_fused_open_supported(4 if t.dtype == torch.float32 else 8, int(radius)))
-
-    def chain_len(self, t, radii, raster_cells):
-        """how many of the windows at the head of ``radii`` one chained / table-free launch takes on a raster of this size
-        (csrc/morph_chain.h; 0 = none)"""
-        import torch
-        # (the library applies its own SMRF_CHAIN / SMRF_FUSED switches here, the ones smrf_progressive_filter_* routes by)
         r = np.ascontiguousarray(np.asarray(radii[:4], dtype=np.int32))
-        return int(self.lib.smrf_pf_chain_length(4 if t.dtype == torch.float32 else 8, r.ctypes.data_as(C.c_void_p), int(r.size),
-                                                 int(raster_cells)))
+        route = np.zeros(r.size, dtype=np.int32)
+        taken = np.zeros(r.size, dtype=np.uint8)
+        _lib.check(self.lib.smrf_pf_plan(4 if t.dtype == torch.float32 else 8, r.ctypes.data_as(C.c_void_p), int(r.size),
+                                         int(img_rows), int(cells), 0, self.impl, 1 if chain else 2,
+                                         route.ctypes.data_as(C.c_void_p), taken.ctypes.data_as(C.c_void_p)))
+        n = 1
+        while route[0] == _lib.ROUTE_CHAIN and n < r.size and route[n] == _lib.ROUTE_CHAIN + n:
+            n += 1
+        return int(route[0]), n
 
     def chain_flag(self, last, last_row0, opened, mask, when, radii, thr, widx, out_row0, out_rows, img_rows):
         """the windows ``radii`` opened one after the other in ONE launch: ``opened`` = the last surface on global rows
@@ -275,31 +279,32 @@ def progressive_filter_sharded(Z_band, img_rows, windows, thresholds, *, rank=No
             gpos += 1
             r = windows[i]
             last = ext[cur]
-            # runs of small windows inside a group as ONE launch (HipBandOps.chain_flag): the margin they eat is the sum of
-            # theirs; not with NaNs (no NaN rule there) and not where the group's last window is split edge-first (overlap)
-            if (world_size > 1 and not nan_aware and not overlap and hasattr(ops, "chain_len")):
-                # sized by the cells a launch of this group marches (a band plus its still-valid margin), not by the whole
-                # raster: the chain 4, 5 and the table-free R = 10 only pay from 20 Mi cells up (chain.hip, min_cells).
-                # The SAME figure on every rank - the longest band with a two-sided margin - so that all ranks route a
-                # window the same way (an edge rank's one-sided margin would otherwise put it on the other side of a size
-                # threshold than its neighbour; every route gives the same bits, but the ranks' launches should not differ).
-                # A chain whose halo is not shorter than the raster has no kernel (smrf_pf_chain_flag_* refuses it).
-                k = ops.chain_len(last, [windows[j] for j in grp[gpos - 1:]], min(img_rows, max_band + 2 * M) * cols)
-                if k >= 1 and sum(2 * windows[j] for j in grp[gpos - 1:gpos - 1 + k]) >= img_rows:
-                    k = 0
-                if k >= 1:
-                    members = grp[gpos - 1:gpos - 1 + k]
-                    lo, hi = max(0, b0 - M), min(img_rows, b1 + M)
-                    M -= sum(2 * windows[j] for j in members)
-                    o0, o1 = max(0, b0 - M), min(img_rows, b1 + M)
-                    nxt = ext[1 - cur]
-                    ops.chain_flag(last[lo - e0:hi - e0], lo, nxt[o0 - e0:o1 - e0], mask[o0 - e0:o1 - e0],
-                                   when[o0 - e0:o1 - e0] if when is not None else None, [windows[j] for j in members],
-                                   [float(thresholds[j]) for j in members], members, o0, o1 - o0, img_rows)
-                    gpos += k - 1
-                    if len(windows) > 1:
-                        cur = 1 - cur
-                    continue
+            # The launch at the head of the windows left in this group, by the library's one routing rule
+            # (HipBandOps.head_launch; ops without it, the oracle-backed ones of the CPU tests, run two passes per window).
+            # Not with NaNs: scipy's NaN rule lives in the two-pass kernels only.  The rule is asked about the cells a launch of
+            # this group marches (a band plus its still-valid margin), not about the whole raster: the chain 4, 5 and the
+            # table-free R = 10 only pay from 20 Mi cells up.  The SAME figure on every rank - the longest band with a two-sided
+            # margin - so that all ranks route a window the same way (an edge rank's one-sided margin would otherwise put it on
+            # the other side of a size threshold than its neighbour; every route gives the same bits, but the ranks' launches
+            # should not differ).  No chains on a single band, nor where the group's last window is split edge-first (overlap).
+            route, k = None, 1
+            if not nan_aware and hasattr(ops, "head_launch"):
+                route, k = ops.head_launch(last, [windows[j] for j in grp[gpos - 1:]], img_rows,
+                                           min(img_rows, max_band + 2 * M) * cols, chain=world_size > 1 and not overlap)
+            if route == _lib.ROUTE_CHAIN:
+                # runs of small windows inside a group as ONE launch (HipBandOps.chain_flag): the margin they eat is the sum of theirs
+                members = grp[gpos - 1:gpos - 1 + k]
+                lo, hi = max(0, b0 - M), min(img_rows, b1 + M)
+                M -= sum(2 * windows[j] for j in members)
+                o0, o1 = max(0, b0 - M), min(img_rows, b1 + M)
+                nxt = ext[1 - cur]
+                ops.chain_flag(last[lo - e0:hi - e0], lo, nxt[o0 - e0:o1 - e0], mask[o0 - e0:o1 - e0],
+                               when[o0 - e0:o1 - e0] if when is not None else None, [windows[j] for j in members],
+                               [float(thresholds[j]) for j in members], members, o0, o1 - o0, img_rows)
+                gpos += k - 1
+                if len(windows) > 1:
+                    cur = 1 - cur
+                continue
             if world_size == 1:
                 lo, hi, q0, q1, o0, o1 = 0, img_rows, 0, img_rows, 0, img_rows
             else:
@@ -309,7 +314,7 @@ def progressive_filter_sharded(Z_band, img_rows, windows, thresholds, *, rank=No
                 o0, o1 = max(0, b0 - M), min(img_rows, b1 + M)          # opening: r more rows inside (the band at the end)
             dst = ero[q0 - e0:q1 - e0]
             nxt = ext[1 - cur]
-            fused = not nan_aware and hasattr(ops, "can_fuse") and ops.can_fuse(last, r)
+            fused = route == _lib.ROUTE_FUSED
             if not fused:
                 ops.erode(last[lo - e0:hi - e0], lo, dst, q0, q1 - q0, img_rows, r, **kw)
 

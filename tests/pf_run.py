@@ -1,5 +1,5 @@
 """progressive_filter through the C ABI with everything the routing tests look at (shared by test_gpu_ero_inc.py and
-test_gpu_incero_edges.py), and the rule of csrc/morph.hip for which windows take the incremental erosion."""
+test_gpu_incero_edges.py), and the rule of csrc/pf_route.h for which windows take the incremental erosion, restated."""
 import ctypes as C
 import os
 import re
@@ -29,6 +29,15 @@ def run_pf(Zd, windows, nan_aware=-1, impl=0):
                   int(nan_aware), int(impl), st, ms.ctypes.data_as(C.c_void_p), route.ctypes.data_as(C.c_void_p)))
     taken = np.zeros(win.size, dtype=np.uint8)
     assert lib.smrf_pf_ero_inc_windows(taken.ctypes.data_as(C.c_void_p), int(win.size)) == win.size
+    # what ran is what the plan says (csrc/pf_route.h through smrf_pf_plan, same arguments; a call with nan_aware < 0 follows the
+    # plan for what the raster holds)
+    has_nan = bool(torch.isnan(Zd).any()) if nan_aware < 0 else nan_aware != 0
+    p_route = np.full(win.size, -1, dtype=np.int32)
+    p_taken = np.full(win.size, 9, dtype=np.uint8)
+    _lib.check(lib.smrf_pf_plan(Zd.element_size(), win.ctypes.data_as(C.c_void_p), int(win.size), rows, rows * cols, int(has_nan),
+                                int(impl), 0, p_route.ctypes.data_as(C.c_void_p), p_taken.ctypes.data_as(C.c_void_p)))
+    assert [int(v) for v in route] == [int(v) for v in p_route], (route, p_route)
+    assert [int(v) for v in taken] == [int(v) for v in p_taken], (taken, p_taken)
     planes = ws.view(Zd.dtype).view(3, rows, cols)
     return mask, when, planes, [int(v) for v in route], [int(v) for v in taken]
 
@@ -43,7 +52,7 @@ def adopted_radii():
 
 
 def inc_rule(windows, route, mode, fp32=True):
-    """morph.hip: window i takes the incremental erosion when it runs as two ring passes, the previous window did too,
+    """pf_route.h, restated independently: window i takes the incremental erosion when it runs as two ring passes, the previous window did too,
     its radius is the previous one's + 1, an instance exists (fp32, 16..64) and, under mode 1, the table adopts the radius"""
     from neilpy_amd import _lib
     adopt = adopted_radii()

@@ -93,7 +93,7 @@ def test_drop_in_signatures_match_the_reference():
 
 
 def test_chain_length_size_thresholds():
-    """smrf_pf_chain_length is host logic (csrc/chain.hip min_cells): which small windows run as chained / table-free launches
+    """smrf_pf_chain_length is host logic (csrc/pf_route.h min_cells): which small windows run as chained / table-free launches
     depends on dtype and raster size.  Round 5 re-measured the thresholds under the new segmentation
     (profiles/r05_segment_balance.md section 7): the chain 4, 5 and the single R = 10 from 20 Mi cells, the single R = 9 and
     the fp64 chain 1, 2, 3 / single R = 5 at any size, the fp64 singles R = 7 / 8 from 4 / 16 Mi cells."""

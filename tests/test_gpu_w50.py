@@ -255,6 +255,28 @@ def test_window_routes_f64(nz, orc, gpu_device, monkeypatch):
     assert np.array_equal(m2.cpu().numpy().astype(bool), want) and np.array_equal(w2.cpu().numpy(), want_w)
 
 
+def test_speculative_first_launch_restarts_on_the_nan_plan(nz, orc, gpu_device, monkeypatch):
+    """nan_aware = -1 on a call whose plan starts with a chain: that launch runs speculatively and carries the NaN scan.  Without a
+    NaN the plan stands (chain 1, 2, 3, then two ring passes, 21 from 20's erosion); with one the plan is made again for a raster
+    with NaNs and the call starts over: two NaN-aware passes per window, no incremental erosion, the oracle's mask and when.
+    (run_pf also holds each report against smrf_pf_plan for what the raster holds.)"""
+    import torch
+    from neilpy_amd import _lib
+    from pf_run import run_pf
+    for name in ("SMRF_FUSED", "SMRF_CHAIN", "SMRF_ERO_INC", "SMRF_NAN_RIDE"):
+        switch(monkeypatch, name, None)
+    win = np.array([1, 2, 3, 20, 21])
+    Zh = nz.synth_dem(600, seed=8, rows=64)
+    Zn = Zh.copy()
+    Zn[41, 333] = np.nan
+    C, TWO = _lib.ROUTE_CHAIN, _lib.ROUTE_TWO_PASS
+    for Z, routes, inc in ((Zh, [C, C + 1, C + 2, TWO, TWO], [0, 0, 0, 0, 1]), (Zn, [TWO] * 5, [0] * 5)):
+        m, w, _, route, taken = run_pf(torch.from_numpy(Z).to(gpu_device), win, nan_aware=-1)
+        assert route == routes and taken == inc
+        want, want_w = orc.progressive_filter(Z, win, 1, .15, return_when_dropped=True)
+        assert np.array_equal(m.cpu().numpy().astype(bool), want) and np.array_equal(w.cpu().numpy(), want_w)
+
+
 def test_unequal_segments_give_the_same_bits(nz, gpu_device, monkeypatch):
     """round 5 (morph_ring.h ring_launch_np, profiles/r05_segment_balance.md): a one-round ring launch cuts the rows into
     segments whose length depends on the residency class of their workgroups (SMRF_RING_SLOPE, permille of the mean length
