@@ -605,6 +605,64 @@ SMRF_API int smrf_voxel_mark_f64(const double* d_x, const double* d_y, const dou
 SMRF_API int smrf_voxel_expand(void* d_workspace, size_t workspace_bytes, int nx, int ny, int nz, int threshold,
                      int bottom_fill, int pad, uint8_t* d_out, void* stream);
 
+/* ---- relief colouring and raster statistics (csrc/relief.hip) ---------------------------
+ * raster_stats: NaN-ignoring statistics of n cells (+-inf are values).  `what` = SMRF_STATS_MOMENTS | SMRF_STATS_MEDIAN;
+ * h_out = a host row of SMRF_STATS_ROW doubles, filled after the stream has been synchronised (one device-to-host copy
+ * per call): the number of non-NaN cells, the number of NaN cells, min, max, mean, the sum of the squares (squared in
+ * the raster's dtype, summed in float64) and the median.  Entries not asked for, and every statistic of an empty or
+ * all-NaN raster, are NaN (the two counts are always set with MOMENTS).  Mean and sum of squares are float64 sums in a
+ * fixed order: per thread a grid-stride chain (thread g of min(ceil(n / 256), 1024) x 256 takes cells g, g + G, ...),
+ * a 64-lane shuffle tree (offsets 32 .. 1), the four waves as (w0 + w1) + (w2 + w3), the workgroups in index order.
+ * The median is np.nanmedian's value, exact: a radix select on an order-preserving integer key, 11 bits per pass
+ * (csrc/select_plan.h).  The u8 instance (MOMENTS only) serves brassel's `any(H > 1)`. */
+#define SMRF_STATS_MOMENTS 1
+#define SMRF_STATS_MEDIAN 2
+#define SMRF_STATS_ROW 8
+#define SMRF_STATS_COUNT 0
+#define SMRF_STATS_NAN 1
+#define SMRF_STATS_MIN 2
+#define SMRF_STATS_MAX 3
+#define SMRF_STATS_MEAN 4
+#define SMRF_STATS_SUM_SQ 5
+#define SMRF_STATS_MEDIAN_AT 6
+SMRF_API size_t smrf_raster_stats_workspace_bytes(int elem_size, int what);
+SMRF_API int smrf_raster_stats_f32(const float* d_X, int64_t n, int what, double* h_out, void* d_workspace,
+                                   size_t workspace_bytes, void* stream);
+SMRF_API int smrf_raster_stats_f64(const double* d_X, int64_t n, int what, double* h_out, void* d_workspace,
+                                   size_t workspace_bytes, void* stream);
+SMRF_API int smrf_raster_stats_u8(const uint8_t* d_X, int64_t n, int what, double* h_out, void* d_workspace,
+                                  size_t workspace_bytes, void* stream);
+/* normalize(): d_out[i] = np.interp(d_X[i], xp, fp) in float64 without FMA; d_knots = xp[n_knots] then fp[n_knots],
+ * float64 on the device, n_knots >= 2, xp non-decreasing. */
+SMRF_API int smrf_normalize_f32(const float* d_X, int64_t n, const double* d_knots, int n_knots, double* d_out,
+                                void* stream);
+SMRF_API int smrf_normalize_f64(const double* d_X, int64_t n, const double* d_knots, int n_knots, double* d_out,
+                                void* stream);
+/* colortable_shade() / swiss_shading(): d_rgb[r][c][0..2] = table[zi][H], with H the uint8 hillshade of
+ * smrf_surface_* (HILLSHADE, spacing = p0, h_angle = one host row cos zenith, sin zenith, azimuth) and
+ * zi = uint8(round(255 * (Z - zmin) / (zmax - zmin))) in the raster's dtype (half-even, NaN -> 0).  zmin / zmax come
+ * from the caller (np.min / np.max: NaN if the raster holds one).  d_lut = 256 x 256 words R | G << 8 | B << 16.
+ * One launch, the raster read once.  rows, cols >= 2 (SMRF_E_ARG below). */
+SMRF_API int smrf_colortable_f32(const float* d_Z, int rows, int cols, double zmin, double zmax, double spacing,
+                                 const double* h_angle, const uint32_t* d_lut, uint8_t* d_rgb, void* stream);
+SMRF_API int smrf_colortable_f64(const double* d_Z, int rows, int cols, double zmin, double zmax, double spacing,
+                                 const double* h_angle, const uint32_t* d_lut, uint8_t* d_rgb, void* stream);
+/* brassel_atmospheric_perspective(): one element-wise launch.  d_H = the shade (h_type: uint8, float32 or float64),
+ * d_Z = the elevations (the entry's dtype); zmin / zmax = np.nanmin / np.nanmax of Z, flat already in 0..1,
+ * logk = log(k).  WAS_INT: H / 255 in float64 and d_out = uint8 round(255 * H_new), cast as NumPy casts on x86 (NaN -> 0,
+ * otherwise the low byte of the signed 32-bit truncation); without it d_out = float64.  ZMID: Zstar is np.interp over
+ * (zmin, zmid, zmax) -> (-1, 0, 1) in float64 instead of the raster-dtype formula. */
+#define SMRF_SHADE_U8 0
+#define SMRF_SHADE_F32 1
+#define SMRF_SHADE_F64 2
+#define SMRF_BRASSEL_WAS_INT 1
+#define SMRF_BRASSEL_ZMID 2
+#define SMRF_BRASSEL_REVERSE 4
+SMRF_API int smrf_brassel_f32(const void* d_H, int h_type, const float* d_Z, int64_t n, int options, double flat,
+                              double zmin, double zmax, double zmid, double logk, double c2, void* d_out, void* stream);
+SMRF_API int smrf_brassel_f64(const void* d_H, int h_type, const double* d_Z, int64_t n, int options, double flat,
+                              double zmin, double zmax, double zmid, double logk, double c2, void* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

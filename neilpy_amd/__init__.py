@@ -13,7 +13,9 @@ stencils under ashift's edge rule, with the host helper ``triangle_height`` (nei
 ``chamfer_distance`` compares two point clouds and ``nearest_points`` is the exact nearest-neighbour query under it, a
 counting sort into a cell grid and a ring search (neilpy_amd/points.py).  ``voxelize`` turns a cloud into the boolean
 voxel model ``np.histogramdd`` and a threshold give, bit for bit: a scatter into a bit set and a byte expansion with the
-bottom fill (neilpy_amd/voxel.py).
+bottom fill (neilpy_amd/voxel.py).  ``colortable_shade`` / ``swiss_shading`` / ``brassel_atmospheric_perspective`` turn a DTM and its
+hillshade into the coloured relief image, over ``raster_stats`` (NaN-ignoring moments in a fixed summation order and an
+exact radix-select median), ``normalize`` and ``rmse`` (neilpy_amd/relief.py).
 """
 from ._lib import SmrfHipError, load as load_library, LIB_PATH          # noqa: F401
 from .affine import Affine, edges_from_IT, from_origin, write_worldfile                 # noqa: F401
@@ -25,6 +27,8 @@ from .las import read_las, read_las_xyz, write_las                         # noq
 from .morphometry import ashift, scaled_morphometry, triangle_height, vip_score   # noqa: F401
 from .nearest import inpaint_nearest, nearest_source                      # noqa: F401
 from .points import chamfer_distance, nearest_points                       # noqa: F401
+from .relief import (brassel_atmospheric_perspective, colortable_shade, cutter, normalize, raster_stats,   # noqa: F401
+                     rmse, swiss_shading)
 from .surface import (aspect, curvature, esri_curvature, esri_slope, evans_curvature, hillshade,   # noqa: F401
                       multiple_illumination, slope, wilson_gallant_curvature, z_factor,
                       zevenbergen_and_thorne_curvature)

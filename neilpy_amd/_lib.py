@@ -24,6 +24,12 @@ SURFACE_OPT_RADIANS, SURFACE_OPT_DEGREES = 1, 2
 # weighted focal sums (include/smrf_hip.h): modes of smrf_focal_*, impl= of neilpy_amd.focal
 FOCAL_SUM, FOCAL_SUM_SQ, FOCAL_STD, FOCAL_TPI = range(4)
 FOCAL_IMPL_AUTO, FOCAL_IMPL_TILED, FOCAL_IMPL_DIRECT = 0, 1, 2
+# raster statistics and relief colouring (include/smrf_hip.h): what= and the result row of smrf_raster_stats_*, the shade
+# types and options of smrf_brassel_*
+STATS_MOMENTS, STATS_MEDIAN, STATS_ROW = 1, 2, 8
+STATS_COUNT, STATS_NAN, STATS_MIN, STATS_MAX, STATS_MEAN, STATS_SUM_SQ, STATS_MEDIAN_AT = range(7)
+SHADE_U8, SHADE_F32, SHADE_F64 = 0, 1, 2
+BRASSEL_WAS_INT, BRASSEL_ZMID, BRASSEL_REVERSE = 1, 2, 4
 
 
 class SmrfHipError(RuntimeError):
@@ -123,6 +129,16 @@ SIGNATURES = {
     "smrf_voxel_mark_f32": (_i, [_p, _p, _p, _i64, C.POINTER(_d), _p, _p, _p, _i, _i, _i, _i, _p, _sz, _p]),
     "smrf_voxel_mark_f64": (_i, [_p, _p, _p, _i64, C.POINTER(_d), _p, _p, _p, _i, _i, _i, _i, _p, _sz, _p]),
     "smrf_voxel_expand": (_i, [_p, _sz, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "smrf_raster_stats_workspace_bytes": (_sz, [_i, _i]),
+    "smrf_raster_stats_f32": (_i, [_p, _i64, _i, C.POINTER(_d), _p, _sz, _p]),
+    "smrf_raster_stats_f64": (_i, [_p, _i64, _i, C.POINTER(_d), _p, _sz, _p]),
+    "smrf_raster_stats_u8": (_i, [_p, _i64, _i, C.POINTER(_d), _p, _sz, _p]),
+    "smrf_normalize_f32": (_i, [_p, _i64, _p, _i, _p, _p]),
+    "smrf_normalize_f64": (_i, [_p, _i64, _p, _i, _p, _p]),
+    "smrf_colortable_f32": (_i, [_p, _i, _i, _d, _d, _d, C.POINTER(_d), _p, _p, _p]),
+    "smrf_colortable_f64": (_i, [_p, _i, _i, _d, _d, _d, C.POINTER(_d), _p, _p, _p]),
+    "smrf_brassel_f32": (_i, [_p, _i, _p, _i64, _i, _d, _d, _d, _d, _d, _d, _p, _p]),
+    "smrf_brassel_f64": (_i, [_p, _i, _p, _i64, _i, _d, _d, _d, _d, _d, _d, _p, _p]),
 }
 
 _lib = None

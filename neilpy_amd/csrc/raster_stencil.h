@@ -60,6 +60,47 @@ struct Evans {
   __device__ inline T K_cross() const { return T(-2) * (B * DD + A * EE - C * D * E) / S2; }
 };
 
+// np.gradient's aspect of one cell, clockwise from north in radians in [0, 2 pi): dy, dx = the differences of the cell's
+// vertical and horizontal neighbours (central inside, one-sided where ey / ex say the cell is on a border), at unit
+// spacing whatever the cellsize.  gy, gx = the gradient (both 0 on a flat; what becomes of A there is the caller's rule).
+template <typename T>
+__device__ inline T aspect_radians(T dy, T dx, bool ey, bool ex, T& gy, T& gx) {
+  using K = Consts<T>;
+  gy = ey ? dy / T(1) : dy / T(2);
+  gx = ex ? dx / T(1) : dx / T(2);
+  T A = K::half_pi - atan2(gy, -gx);
+  if (A < T(0)) A = A + K::two_pi;
+  return A;
+}
+
+// hillshade of one cell: slope and aspect in T from the same differences, the illumination in
+// float64 over a table of n_ang rows (cos zenith, sin zenith, azimuth).  Returns the largest uint8 shade round(255 H)
+// over the rows (NaN -> 0); H = the last row's float shade.  hillshade, multiple_illumination (surface.hip) and
+// colortable_shade (relief.hip) all shade through this one function, spacing = cellsize / z_factor.
+template <typename T>
+__device__ inline int hillshade_cell(T dy, T dx, bool ey, bool ex, double spacing, const double* ang, int n_ang,
+                                     double& H) {
+  T gy, gx;
+  T A = aspect_radians<T>(dy, dx, ey, ex, gy, gx);
+  if (gx == T(0) && gy == T(0)) A = T(0);
+  const T h = (T)spacing, h2 = (T)(2.0 * spacing);
+  const T sy = ey ? dy / h : dy / h2;
+  const T sx = ex ? dx / h : dx / h2;
+  const T S = atan(sqrt(sx * sx + sy * sy));
+  const double cs = (double)cos(S), sn = (double)sin(S), Ad = (double)A;
+  int best = 0;
+  H = 0.0;
+  for (int k = 0; k < n_ang; ++k) {
+    const double* g = ang + 3 * k;
+    H = (g[0] * cs) + (g[1] * sn * cos(g[2] - Ad));
+    if (H < 0.0) H = 0.0;
+    const double v = rint(255.0 * H);
+    const int u = v != v ? 0 : (int)v;   // NaN -> 0, as the x86 conversion gives
+    best = u > best ? u : best;
+  }
+  return best;
+}
+
 // ---- host: the checks of every raster entry point, with the status codes and texts callers read from smrf_last_error()
 inline int check_size(int rows, int cols, int count = 0) {
   return (rows < 0 || cols < 0 || count < 0) ? smrf_fail(SMRF_E_ARG, "negative size") : SMRF_OK;

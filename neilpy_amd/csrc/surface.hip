@@ -64,38 +64,19 @@ __device__ inline void cell(const SurfArgs<T>& a, const Win<T>& w, long long idx
     const T dy = w.n[2][1] - w.n[0][1];
     const T dx = w.n[1][2] - w.n[1][0];
     const bool ey = top || bot, ex = lft || rgt;
-    if constexpr (MODE == SMRF_SURFACE_ASPECT || MODE == SMRF_SURFACE_HILLSHADE) {
-      // aspect: unit spacing whatever the cellsize
-      const T gy = ey ? dy / T(1) : dy / T(2);
-      const T gx = ex ? dx / T(1) : dx / T(2);
-      T A = K::half_pi - atan2(gy, -gx);
-      if (A < T(0)) A = A + K::two_pi;
-      if constexpr (MODE == SMRF_SURFACE_ASPECT) {
-        if (a.opts & SMRF_SURFACE_OPT_DEGREES) A = A * K::rad2deg;
-        if (gx == T(0) && gy == T(0)) A = (T)a.p0;   // flat_as
-        put<T>(a.out[0], idx, A);
-        return;
-      } else {
-        if (gx == T(0) && gy == T(0)) A = T(0);
-        const T h = (T)a.p0, h2 = (T)(2.0 * a.p0);
-        const T sy = ey ? dy / h : dy / h2;
-        const T sx = ex ? dx / h : dx / h2;
-        const T S = atan(sqrt(sx * sx + sy * sy));
-        const double cs = (double)cos(S), sn = (double)sin(S), Ad = (double)A;
-        int best = 0;
-        double H = 0.0;
-        for (int k = 0; k < a.n_ang; ++k) {
-          const double* g = a.ang + 3 * k;
-          H = (g[0] * cs) + (g[1] * sn * cos(g[2] - Ad));
-          if (H < 0.0) H = 0.0;
-          const double v = rint(255.0 * H);
-          const int u = v != v ? 0 : (int)v;   // NaN -> 0, as the x86 conversion gives
-          best = u > best ? u : best;
-        }
-        put<uint8_t>(a.out[0], idx, (uint8_t)best);
-        put<double>(a.out[1], idx, H);
-        return;
-      }
+    if constexpr (MODE == SMRF_SURFACE_HILLSHADE) {
+      double H;
+      const int best = hillshade_cell<T>(dy, dx, ey, ex, a.p0, a.ang, a.n_ang, H);   // raster_stencil.h
+      put<uint8_t>(a.out[0], idx, (uint8_t)best);
+      put<double>(a.out[1], idx, H);
+      return;
+    } else if constexpr (MODE == SMRF_SURFACE_ASPECT) {
+      T gy, gx;
+      T A = aspect_radians<T>(dy, dx, ey, ex, gy, gx);
+      if (a.opts & SMRF_SURFACE_OPT_DEGREES) A = A * K::rad2deg;
+      if (gx == T(0) && gy == T(0)) A = (T)a.p0;   // flat_as
+      put<T>(a.out[0], idx, A);
+      return;
     } else {
       const T h = (T)a.p0, h2 = (T)(2.0 * a.p0);
       const T gy = ey ? dy / h : dy / h2;
