@@ -15,12 +15,14 @@ surface the previous group leaves.  That group's last dilation is split: the two
 a side stream, followed by the exchange; the interior runs beside them on the main stream, which only
 waits for the exchange before the next group's first erosion.
 
-The communication uses ``torch.distributed`` point-to-point ops, so the same driver runs on
-``nccl`` (= RCCL) with CUDA tensors and on ``gloo`` with CPU tensors; the compute is delegated
-to a ``BandOps`` object.  The product default is :class:`HipBandOps` (libsmrf_hip); the CPU tests
-inject an oracle-backed ops object to exercise the partitioning and halo logic without a GPU.
+The communication goes through one :class:`BandComm` (``torch.distributed``: ``nccl`` = RCCL with CUDA tensors, ``gloo``
+with CPU tensors), the compute through a ``BandOps`` object (the product default is :class:`HipBandOps`, libsmrf_hip), and
+the row arithmetic between them is :func:`band_plan`, a pure function.  Every entry point takes ``ops=`` and ``comm=``: the
+CPU tests inject an oracle-backed ops object, the one-GPU tests a communicator that plays the neighbours.
 """
+import collections
 import ctypes as C
+import itertools
 
 import numpy as np
 
@@ -36,6 +38,101 @@ def band_rows(img_rows, world_size, rank):
     base, rem = divmod(img_rows, world_size)
     b0 = rank * base + min(rank, rem)
     return b0, b0 + base + (1 if rank < rem else 0)
+
+
+def band_sizes(img_rows, world_size):
+    """Rows of every rank's band."""
+    return [b1 - b0 for b0, b1 in (band_rows(img_rows, world_size, k) for k in range(world_size))]
+
+
+class BandComm:
+    """The ranks of one call: ``rank``, ``world``, ``multi`` (more than one rank), ``live`` (a process group is initialised),
+    ``gloo``, and every message the row-band entry points send.  ONE staging rule underneath all of them: CUDA tensors on a
+    gloo group (multi-process rehearsals on a one-GPU box) travel through host memory; anything else goes straight to
+    the backend (nccl = RCCL moves the CUDA blocks over xGMI).  A subclass that overrides :meth:`exchange` stands in for
+    the neighbours (tests/sharded_one_gpu.py, tools/band_compute.py)."""
+
+    def __init__(self, group=None, rank=None, world_size=None):
+        import torch.distributed as dist
+        self.dist, self.group, self.live = dist, group, dist.is_initialized()
+        self.world = world_size if world_size is not None else (dist.get_world_size(group) if self.live else 1)
+        self.rank = rank if rank is not None else (dist.get_rank(group) if self.live else 0)
+        self.multi = self.world > 1
+        self.gloo = self.live and dist.get_backend(group) == "gloo"
+
+    def _staged(self, *tensors):
+        return self.gloo and any(t is not None and t.is_cuda for t in tensors)
+
+    def sendrecv(self, pairs):
+        """One batch of ``(send | None, recv | None, peer rank)``: per peer the send, then the recv, in the order given;
+        a peer beyond the first or last rank is skipped."""
+        dist, group = self.dist, self.group
+        staged = self._staged(*[t for snd, rcv, _ in pairs for t in (snd, rcv)])
+        ops, back = [], []
+        for snd, rcv, p in pairs:
+            if not 0 <= p < self.world:
+                continue
+            p = dist.get_global_rank(group, p) if group is not None else p
+            if snd is not None:                              # (row blocks of the halo are contiguous already)
+                ops.append(dist.P2POp(dist.isend, snd.cpu() if staged else snd.contiguous(), p, group))
+            if rcv is not None:
+                if staged:
+                    back.append((rcv, rcv.cpu()))
+                ops.append(dist.P2POp(dist.irecv, back[-1][1] if staged else rcv, p, group))
+        if ops:
+            for req in dist.batch_isend_irecv(ops):
+                req.wait()
+        for dst, h in back:
+            dst.copy_(h)
+
+    def exchange(self, send_up, recv_up, send_down, recv_down):
+        """send_up -> rank-1 (its bottom halo), send_down -> rank+1 (its top halo); the upper neighbour first."""
+        self.sendrecv([(send_up, recv_up, self.rank - 1), (send_down, recv_down, self.rank + 1)])
+
+    def shift(self, send, recv, up):
+        """up=True: every rank sends `send` to rank-1 and receives `recv` from rank+1 (down: the reverse)."""
+        dst, src = (self.rank - 1, self.rank + 1) if up else (self.rank + 1, self.rank - 1)
+        self.sendrecv([(send, None, dst), (None, recv, src)])
+
+    def all_reduce(self, t, op="SUM"):
+        """in place"""
+        h = t.cpu() if self._staged(t) else t
+        self.dist.all_reduce(h, op=getattr(self.dist.ReduceOp, op), group=self.group)
+        if h is not t:
+            t.copy_(h)
+
+    def reduced(self, value, dtype, op, device):
+        """``value`` (a number, or a list of them) reduced over the ranks, as Python numbers; the message is made on
+        ``device`` unless the group is gloo.  One rank: ``value`` itself."""
+        import torch
+        if not self.multi:
+            return value
+        t = torch.tensor(value if isinstance(value, list) else [value], dtype=dtype, device="cpu" if self.gloo else device)
+        self.dist.all_reduce(t, op=getattr(self.dist.ReduceOp, op), group=self.group)
+        return t.tolist() if isinstance(value, list) else t.item()
+
+    def all_to_all(self, out, inp, out_splits=None, in_splits=None):
+        """all_to_all_single"""
+        h = out.cpu() if self._staged(inp) else out
+        self.dist.all_to_all_single(h, inp.cpu() if h is not out else inp, output_split_sizes=out_splits,
+                                    input_split_sizes=in_splits, group=self.group)
+        if h is not out:
+            out.copy_(h)
+
+    def all_gather_rows(self, part, sizes):
+        """Concatenate every rank's leading-dimension block (``sizes[k]`` rows on rank k) on every rank.
+        Blocks are padded to the largest one (all_gather wants equal shapes)."""
+        import torch
+        if not self.multi:
+            return part
+        buf = torch.zeros((max(sizes),) + tuple(part.shape[1:]), dtype=part.dtype, device=part.device)
+        buf[:part.shape[0]].copy_(part)
+        staged = self._staged(part)
+        src = buf.cpu() if staged else buf
+        outs = [torch.empty_like(src) for _ in sizes]
+        self.dist.all_gather(outs, src, group=self.group)
+        full = torch.cat([o[:n] for o, n in zip(outs, sizes)], dim=0)
+        return full.to(part.device) if staged else full
 
 
 class HipBandOps:
@@ -107,36 +204,6 @@ class HipBandOps:
                       _stream()))
 
 
-def _exchange(dist, group, rank, world, send_up, recv_up, send_down, recv_down):
-    """send_up -> rank-1 (its bottom halo), send_down -> rank+1 (its top halo).
-
-    nccl (= RCCL) moves the CUDA row blocks directly over xGMI.  On a gloo group (the CPU tests,
-    and multi-process rehearsals on a one-GPU box) CUDA tensors are staged through host memory.
-    """
-    def peer(r):
-        return dist.get_global_rank(group, r) if group is not None else r
-    staged = dist.get_backend(group) == "gloo" and any(t is not None and t.is_cuda
-                                                       for t in (send_up, recv_up, send_down, recv_down))
-    pairs = []
-    if rank > 0:
-        pairs.append((send_up, recv_up, peer(rank - 1)))
-    if rank < world - 1:
-        pairs.append((send_down, recv_down, peer(rank + 1)))
-    ops, back = [], []
-    for snd, rcv, p in pairs:
-        if staged:
-            h_s, h_r = snd.cpu(), rcv.cpu()
-            back.append((rcv, h_r))
-            snd, rcv = h_s, h_r
-        ops.append(dist.P2POp(dist.isend, snd, p, group))
-        ops.append(dist.P2POp(dist.irecv, rcv, p, group))
-    if ops:
-        for req in dist.batch_isend_irecv(ops):
-            req.wait()
-    for dst, h in back:
-        dst.copy_(h)
-
-
 def window_groups(windows, min_band_rows, budget=None):
     """Consecutive windows that share ONE halo exchange: a group needs sum(2r) rows of the
     neighbours' bands up front and recomputes its margins redundantly while they shrink by 2r per
@@ -160,14 +227,95 @@ def window_groups(windows, min_band_rows, budget=None):
     return groups
 
 
+Step = collections.namedtuple("Step", "kind group members src dst in0 in1 out0 out1 side halo")
+Step.__doc__ = """One call of the band driver, rows as GLOBAL ranges [x0, x1); ``group``: its window group; ``side``: on
+the side stream (the edge-first split of ``overlap``).  ``kind``:
+``exchange``  ``halo`` rows with each neighbour on surface buffer ``src``: the band [in0, in1) is valid before, [out0, out1) after;
+``chain``     windows ``members`` in one launch: reads buffer ``src`` on [in0, in1), writes ``dst`` on [out0, out1);
+``erode``     window ``members[0]``: reads ``src`` on [in0, in1), writes the erosion buffer on [out0, out1);
+``open``      fused opening + flags: reads ``src`` on [in0, in1), writes ``dst`` on [out0, out1);
+``dilate``    dilation + flags: reads the erosion on [in0, in1) and ``src`` on [out0, out1), writes ``dst`` on [out0, out1)."""
+
+
+def band_plan(img_rows, world, rank, windows, groups, overlap=False, head=None):
+    """The steps (:class:`Step`) ``rank`` runs for the window ``groups`` (lists of indices into ``windows``, the radii), in
+    order: the row arithmetic of :func:`progressive_filter_sharded` and nothing else (no torch, no process group).
+
+    A group starts with ONE exchange of M = sum(2r) rows, after which ``last`` is valid on the band plus M rows either
+    side (clipped to the raster).  Every window erodes r rows inside the valid rows and opens r more rows inside, so
+    the margin shrinks by 2r per window and is zero - the band itself - at the group's end.  With ``overlap`` the
+    group's last dilation is split edge-first where the band holds the 2 * Mn rows: the two Mn-row edge pieces and the
+    NEXT group's exchange (the neighbours need exactly those rows of the opened surface) go to the side stream, the
+    interior follows; that next group then starts without an exchange.  Otherwise the exchange sits at its group's head.
+    One band (``world == 1``): no exchange, whole-raster ranges.  The two surface buffers swap roles after every launch
+    that writes one, unless there is a single window.
+
+    ``head(src, radii, rows, chain) -> (route, n)`` answers what ``HipBandOps.head_launch`` answers for the windows
+    ``radii`` left in a group; None (ops without a routing rule, or a NaN-aware call): two passes per window.  It is asked
+    about ``rows`` = the rows a launch of this group marches, the longest band with a two-sided margin: the SAME figure
+    on every rank, so that all ranks route a window the same way (an edge rank's one-sided margin would otherwise put it
+    on the other side of a size threshold than its neighbour; every route gives the same bits, but the ranks' launches
+    should not differ).  ``chain`` is off on a single band and where the group's last window may be split (overlap).
+    A generator: ``head`` is asked about a window when the consumer reaches it.
+    """
+    b0, b1 = band_rows(img_rows, world, rank)
+    multi = world > 1
+    max_band = max(band_sizes(img_rows, world))
+    halo = [sum(2 * windows[i] for i in g) if multi else 0 for g in groups]
+
+    def span(m):                                             # the band and m rows either side
+        return (max(0, b0 - m), min(img_rows, b1 + m)) if multi else (0, img_rows)
+    cur, early = 0, False                                    # early: this group's exchange ran inside the previous group's split
+    for gi, grp in enumerate(groups):
+        M = halo[gi]                                         # rows of `last` still valid beyond the band,
+        lo, hi = span(M)                                     # and the rows that are valid
+        if M > 0 and not early:
+            yield Step("exchange", gi, [], cur, cur, b0, b1, lo, hi, False, M)
+        early, pos = False, 0
+        while pos < len(grp):
+            i, r = grp[pos], windows[grp[pos]]
+            route, k = (None, 1) if head is None else head(cur, [windows[j] for j in grp[pos:]],
+                                                           min(img_rows, max_band + 2 * M), multi and not overlap)
+            if route == _lib.ROUTE_CHAIN:                    # a run of small windows: the margin they eat is the sum of theirs
+                members = grp[pos:pos + k]
+                M = max(0, M - sum(2 * windows[j] for j in members))
+                o0, o1 = span(M)
+                yield Step("chain", gi, members, cur, 1 - cur, lo, hi, o0, o1, False, 0)
+                pos += k
+            else:
+                q0, q1 = span(M - r)                         # erosion: r rows inside the valid ones
+                M = max(0, M - 2 * r)
+                o0, o1 = span(M)                             # opening: r more rows inside (the band at the group's end)
+                pos += 1
+                if route == _lib.ROUTE_FUSED:
+                    kind, in0, in1 = "open", lo, hi
+                else:
+                    kind, in0, in1 = "dilate", q0, q1
+                    yield Step("erode", gi, [i], cur, None, lo, hi, q0, q1, False, 0)
+                # margin rows are flagged too (same values the neighbour computes for them); only the band's are returned
+                Mn = halo[gi + 1] if overlap and pos == len(grp) and gi + 1 < len(groups) else 0
+                if Mn > 0 and o0 == b0 and o1 == b1 and b1 - b0 >= 2 * Mn:
+                    yield Step(kind, gi, [i], cur, 1 - cur, in0, in1, b0, b0 + Mn, True, 0)
+                    yield Step(kind, gi, [i], cur, 1 - cur, in0, in1, b1 - Mn, b1, True, 0)
+                    yield Step("exchange", gi, [], 1 - cur, 1 - cur, b0, b1, *span(Mn), True, Mn)
+                    if b1 - b0 > 2 * Mn:
+                        yield Step(kind, gi, [i], cur, 1 - cur, in0, in1, b0 + Mn, b1 - Mn, False, 0)
+                    early = True
+                else:
+                    yield Step(kind, gi, [i], cur, 1 - cur, in0, in1, o0, o1, False, 0)
+            lo, hi = o0, o1                                  # what this launch wrote is what the next one may read
+            if len(windows) > 1:
+                cur = 1 - cur
+
+
 def progressive_filter_sharded(Z_band, img_rows, windows, thresholds, *, rank=None, world_size=None, group=None,
-                               ops=None, return_when_dropped=False, state=None, halo_budget=None, overlap=False):
+                               ops=None, return_when_dropped=False, state=None, halo_budget=None, overlap=False, comm=None):
     """progressive_filter on this rank's row band ``Z_band`` (rows ``band_rows(img_rows, W, rank)``).
 
     Returns the band's ``(mask, when_dropped | None)`` as uint8 tensors on ``Z_band``'s device.
     ``thresholds`` = ``slope_threshold * (windows * cellsize)`` in float64, as on one device.
     Every band must have at least ``2 * max(windows)`` rows (a halo never spans two ranks).
-    ``state`` (a dict) keeps the extended buffers between calls so a benchmark loop does not
+    ``state`` (a dict) keeps the extended buffers and their row views between calls so a benchmark loop does not
     re-allocate (and reports ``state["exchanges"]``; with ``state["profile"] = True`` also ``exchange_events``, a pair
     of CUDA events around every exchange, ``exchange_bytes``, the bytes this rank sent in each, and ``groups``).  ``halo_budget``: rows of halo a group of
     consecutive windows may share in one exchange (see :func:`window_groups`; 0 = one exchange
@@ -175,13 +323,12 @@ def progressive_filter_sharded(Z_band, img_rows, windows, thresholds, *, rank=No
     on a side stream beside the interior (module docstring).  Off by default: on a 2048-row band the two edge
     strips cost about 160 us per group, more than an exchange of up to about 0.45 ms returns
     (tools/band_compute.py, gpurun_out/r02/band_compute.log); it pays on slower links only.
+    ``comm``: the :class:`BandComm` to use instead of one built from ``group`` / ``rank`` / ``world_size``.
     """
     import torch
-    import torch.distributed as dist
-    if world_size is None:
-        world_size = dist.get_world_size(group) if dist.is_initialized() else 1
-    if rank is None:
-        rank = dist.get_rank(group) if dist.is_initialized() else 0
+    if comm is None:
+        comm = BandComm(group, rank, world_size)
+    rank, world_size = comm.rank, comm.world
     if ops is None:
         ops = HipBandOps()
     windows = [int(w) for w in np.asarray(windows).ravel()]
@@ -194,16 +341,13 @@ def progressive_filter_sharded(Z_band, img_rows, windows, thresholds, *, rank=No
         raise ValueError("band has %d rows, expected %d" % (Z_band.shape[0], nloc))
     cols = Z_band.shape[1]
     rmax = max(windows) if windows else 0
-    min_band = min(band_rows(img_rows, world_size, k)[1] - band_rows(img_rows, world_size, k)[0]
-                   for k in range(world_size))
-    max_band = max(band_rows(img_rows, world_size, k)[1] - band_rows(img_rows, world_size, k)[0]
-                   for k in range(world_size))
-    if world_size > 1 and min_band < 2 * rmax:
+    min_band = min(band_sizes(img_rows, world_size))
+    if comm.multi and min_band < 2 * rmax:
         raise ValueError("row bands of %d rows are shorter than the 2*%d halo rows a window needs; "
                          "use fewer ranks for this raster" % (min_band, rmax))
     dev, dt = Z_band.device, Z_band.dtype
-    groups = window_groups(windows, min_band, halo_budget) if world_size > 1 else [[i] for i in range(len(windows))]
-    H = max([sum(2 * windows[i] for i in g) for g in groups], default=0) if world_size > 1 else 0
+    groups = window_groups(windows, min_band, halo_budget) if comm.multi else [[i] for i in range(len(windows))]
+    H = max([sum(2 * windows[i] for i in g) for g in groups], default=0) if comm.multi else 0
     e0, e1 = max(0, b0 - H), min(img_rows, b1 + H)          # rows the extended buffers can hold
     st = state if state is not None else {}
     key = (nloc, cols, H, str(dt), str(dev))
@@ -222,142 +366,91 @@ def progressive_filter_sharded(Z_band, img_rows, windows, thresholds, *, rank=No
     mask.zero_()
     if when is not None:
         when.zero_()
-    off = b0 - e0                                            # band's first row inside an ext buffer
-    cur = 0
-    ext[cur][off:off + nloc].copy_(Z_band)
+    ext[0][b0 - e0:b1 - e0].copy_(Z_band)
     st["exchanges"] = 0
     # scipy's NaN rule (first visited footprint element decides) costs the kernels a read per cell: only when some
     # band holds a NaN, as the single-device path decides with one count
     nan_aware = 0
     if hasattr(ops, "has_nan"):
         nan_aware = int(bool(ops.has_nan(Z_band)))
-        if world_size > 1 and dist.is_initialized():
-            flag = torch.tensor([nan_aware], dtype=torch.int32, device=dev if dist.get_backend(group) != "gloo" else "cpu")
-            dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=group)
-            nan_aware = int(flag.item())
+        if comm.live:
+            nan_aware = comm.reduced(nan_aware, torch.int32, "MAX", dev)
     kw = {"nan_aware": nan_aware} if nan_aware else {}
     # overlap (CUDA tensors): the exchange a group needs is posted on a side stream as soon as the previous group's
     # last dilation has produced the band's edge rows, and runs beside that dilation's interior
     side = st.get("side")
-    if side is None and Z_band.is_cuda and world_size > 1:
+    if side is None and Z_band.is_cuda and comm.multi:
         side = st["side"] = torch.cuda.Stream(device=dev)
-    M_of = [sum(2 * windows[i] for i in g) if world_size > 1 else 0 for g in groups]
     st["groups"] = [[windows[i] for i in g] for g in groups]
-
     profile = bool(st.get("profile")) and Z_band.is_cuda      # bench.py: events either side of every exchange
     if profile:
         st["exchange_events"], st["exchange_bytes"] = [], []
 
-    def exchange(last, M):
-        lo, hi = max(0, b0 - M), min(img_rows, b1 + M)
-        if profile:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        _exchange(dist, group, rank, world_size,
-                  last[off:off + M], last[lo - e0:off] if rank > 0 else None,
-                  last[off + nloc - M:off + nloc], last[off + nloc:hi - e0] if rank < world_size - 1 else None)
-        if profile:
-            ev1.record()
-            st["exchange_events"].append((ev0, ev1))
-            st["exchange_bytes"].append(M * cols * Z_band.element_size() * ((rank > 0) + (rank < world_size - 1)))
-        st["exchanges"] += 1
+    # The launch at the head of the windows left in a group, by the library's one routing rule (ops without it, the oracle-backed
+    # ones of the CPU tests, run two passes per window).  Not with NaNs: scipy's NaN rule lives in the two-pass kernels only.
+    # Asked about the cells a launch marches, not the whole raster: the chain 4, 5 and the table-free R = 10 only pay from 20 Mi up.
+    def head(src, radii, rows, chain):
+        return ops.head_launch(ext[src], radii, img_rows, rows * cols, chain=chain)
+    plan = band_plan(img_rows, world_size, rank, windows, groups, overlap,
+                     head if not nan_aware and hasattr(ops, "head_launch") else None)
+    views = st.setdefault("views", {})                       # row views of the buffers, kept with them between calls
 
-    posted = None                                            # event of an exchange posted ahead for the next group
-    for gi, grp in enumerate(groups):
-        # rows of `last` the whole group needs beyond the band: every opening eats 2r of them
-        M = M_of[gi]
-        if M > 0:
-            if posted is not None:
-                if posted is not True:
-                    torch.cuda.current_stream().wait_event(posted)
-                posted = None
-            else:
-                exchange(ext[cur], M)
-        gpos = 0
-        while gpos < len(grp):
-            i = grp[gpos]
-            gpos += 1
-            r = windows[i]
-            last = ext[cur]
-            # The launch at the head of the windows left in this group, by the library's one routing rule
-            # (HipBandOps.head_launch; ops without it, the oracle-backed ones of the CPU tests, run two passes per window).
-            # Not with NaNs: scipy's NaN rule lives in the two-pass kernels only.  The rule is asked about the cells a launch of
-            # this group marches (a band plus its still-valid margin), not about the whole raster: the chain 4, 5 and the
-            # table-free R = 10 only pay from 20 Mi cells up.  The SAME figure on every rank - the longest band with a two-sided
-            # margin - so that all ranks route a window the same way (an edge rank's one-sided margin would otherwise put it on
-            # the other side of a size threshold than its neighbour; every route gives the same bits, but the ranks' launches
-            # should not differ).  No chains on a single band, nor where the group's last window is split edge-first (overlap).
-            route, k = None, 1
-            if not nan_aware and hasattr(ops, "head_launch"):
-                route, k = ops.head_launch(last, [windows[j] for j in grp[gpos - 1:]], img_rows,
-                                           min(img_rows, max_band + 2 * M) * cols, chain=world_size > 1 and not overlap)
-            if route == _lib.ROUTE_CHAIN:
-                # runs of small windows inside a group as ONE launch (HipBandOps.chain_flag): the margin they eat is the sum of theirs
-                members = grp[gpos - 1:gpos - 1 + k]
-                lo, hi = max(0, b0 - M), min(img_rows, b1 + M)
-                M -= sum(2 * windows[j] for j in members)
-                o0, o1 = max(0, b0 - M), min(img_rows, b1 + M)
-                nxt = ext[1 - cur]
-                ops.chain_flag(last[lo - e0:hi - e0], lo, nxt[o0 - e0:o1 - e0], mask[o0 - e0:o1 - e0],
-                               when[o0 - e0:o1 - e0] if when is not None else None, [windows[j] for j in members],
-                               [float(thresholds[j]) for j in members], members, o0, o1 - o0, img_rows)
-                gpos += k - 1
-                if len(windows) > 1:
-                    cur = 1 - cur
-                continue
-            if world_size == 1:
-                lo, hi, q0, q1, o0, o1 = 0, img_rows, 0, img_rows, 0, img_rows
-            else:
-                lo, hi = max(0, b0 - M), min(img_rows, b1 + M)          # rows of `last` that are valid now
-                q0, q1 = max(0, b0 - M + r), min(img_rows, b1 + M - r)  # erosion: r rows inside them
-                M -= 2 * r
-                o0, o1 = max(0, b0 - M), min(img_rows, b1 + M)          # opening: r more rows inside (the band at the end)
-            dst = ero[q0 - e0:q1 - e0]
-            nxt = ext[1 - cur]
-            fused = route == _lib.ROUTE_FUSED
-            if not fused:
-                ops.erode(last[lo - e0:hi - e0], lo, dst, q0, q1 - q0, img_rows, r, **kw)
+    def cut(t, y0, y1):                                      # global rows [y0, y1) of an extended buffer
+        k = (id(t), y0, y1)
+        if k not in views:
+            views[k] = t[y0 - e0:y1 - e0] if t is not None else None
+        return views[k]
 
-            def dilate(y0, y1):
-                # margin rows are flagged too (same values the neighbour computes for them); only the band's are returned
-                if fused:                                    # small disk: opening + flag of these rows in one launch
-                    ops.open_flag(last[lo - e0:hi - e0], lo, nxt[y0 - e0:y1 - e0], mask[y0 - e0:y1 - e0],
-                                  when[y0 - e0:y1 - e0] if when is not None else None, float(thresholds[i]), i, y0, y1 - y0,
-                                  img_rows, r)
-                    return
-                ops.dilate_flag(dst, q0, q1 - q0, last[y0 - e0:y1 - e0], nxt[y0 - e0:y1 - e0], mask[y0 - e0:y1 - e0],
-                                when[y0 - e0:y1 - e0] if when is not None else None, float(thresholds[i]), i, y0, y1 - y0,
-                                img_rows, r, **kw)
-            Mn = M_of[gi + 1] if (overlap and i == grp[-1] and gi + 1 < len(groups)) else 0
-            if Mn > 0 and o0 == b0 and o1 == b1 and nloc >= 2 * Mn:
-                # last window of the group: the Mn edge rows either side first, then the next group's exchange beside
-                # the interior (the neighbours need exactly those rows of the opened surface)
-                if side is not None:
-                    ready = torch.cuda.Event()
-                    ready.record()                                       # the erosion is enqueued before this point
-                    with torch.cuda.stream(side):
-                        side.wait_event(ready)
-                        dilate(b0, b0 + Mn)
-                        dilate(b1 - Mn, b1)
-                        exchange(nxt, Mn)
-                        posted = torch.cuda.Event()
-                        posted.record()
-                    if nloc > 2 * Mn:
-                        dilate(b0 + Mn, b1 - Mn)
-                else:                                                    # CPU tensors (gloo tests): same split, in order
-                    dilate(b0, b0 + Mn)
-                    dilate(b1 - Mn, b1)
-                    exchange(nxt, Mn)
-                    posted = True
-                    if nloc > 2 * Mn:
-                        dilate(b0 + Mn, b1 - Mn)
-            else:
-                dilate(o0, o1)
-            if len(windows) > 1:
-                cur = 1 - cur
+    def run(s):
+        last, out = ext[s.src], (s.out0, s.out1)
+        if s.kind == "exchange":
+            if profile:
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ev0.record()
+            comm.exchange(cut(last, b0, b0 + s.halo), cut(last, s.out0, b0) if rank > 0 else None,
+                          cut(last, b1 - s.halo, b1), cut(last, b1, s.out1) if rank < world_size - 1 else None)
+            if profile:
+                ev1.record()
+                st["exchange_events"].append((ev0, ev1))
+                st["exchange_bytes"].append(s.halo * cols * Z_band.element_size() * ((rank > 0) + (rank < world_size - 1)))
+            st["exchanges"] += 1
+            return
+        i = s.members[0]
+        if s.kind == "erode":
+            ops.erode(cut(last, s.in0, s.in1), s.in0, cut(ero, *out), s.out0, s.out1 - s.out0, img_rows, windows[i], **kw)
+            return
+        dst = cut(ext[s.dst], *out), cut(mask, *out), cut(when, *out)
+        if s.kind == "chain":
+            ops.chain_flag(cut(last, s.in0, s.in1), s.in0, *dst, [windows[j] for j in s.members],
+                           [float(thresholds[j]) for j in s.members], s.members, s.out0, s.out1 - s.out0, img_rows)
+        elif s.kind == "open":
+            ops.open_flag(cut(last, s.in0, s.in1), s.in0, *dst, float(thresholds[i]), i, s.out0, s.out1 - s.out0, img_rows,
+                          windows[i])
+        else:
+            ops.dilate_flag(cut(ero, s.in0, s.in1), s.in0, s.in1 - s.in0, cut(last, *out), *dst, float(thresholds[i]), i,
+                            s.out0, s.out1 - s.out0, img_rows, windows[i], **kw)
+
+    posted, g = None, 0
+    for (gi, on_side), steps in itertools.groupby(plan, key=lambda s: (s.group, s.side and side is not None)):
+        if gi != g and posted is not None:                   # the next group's first read waits for the exchange posted ahead
+            torch.cuda.current_stream().wait_event(posted)
+            posted = None
+        g = gi
+        if on_side:                                          # edge pieces, then the next group's exchange, beside the interior
+            ready = torch.cuda.Event()
+            ready.record()                                   # the erosion is enqueued before this point
+            with torch.cuda.stream(side):
+                side.wait_event(ready)
+                for s in steps:
+                    run(s)
+                posted = torch.cuda.Event()
+                posted.record()
+        else:                                                # the main stream (CPU tensors, the gloo tests: every step, in order)
+            for s in steps:
+                run(s)
     if side is not None:
         torch.cuda.current_stream().wait_stream(side)        # nothing of this call is left running on the side stream
-    return mask[off:off + nloc], (when[off:off + nloc] if when is not None else None)
+    return mask[b0 - e0:b1 - e0], (when[b0 - e0:b1 - e0] if when is not None else None)
 
 
 # ------------------------------------------------------------------------------------------
@@ -409,40 +502,8 @@ class HipSpringsOps:
         return istop.value, itn.value, nunk.value, bool(done.value)
 
 
-def _shift(dist, group, rank, world, send, recv, up):
-    """up=True: every rank sends `send` to rank-1 and receives `recv` from rank+1 (down: the reverse)."""
-    dst, src = (rank - 1, rank + 1) if up else (rank + 1, rank - 1)
-
-    def peer(r):
-        return dist.get_global_rank(group, r) if group is not None else r
-    staged = dist.get_backend(group) == "gloo" and send.is_cuda
-    ops, back = [], None
-    if 0 <= dst < world:
-        ops.append(dist.P2POp(dist.isend, send.cpu() if staged else send.contiguous(), peer(dst), group))
-    if 0 <= src < world:
-        if staged:
-            back = recv.cpu()
-            ops.append(dist.P2POp(dist.irecv, back, peer(src), group))
-        else:
-            ops.append(dist.P2POp(dist.irecv, recv, peer(src), group))
-    if ops:
-        for req in dist.batch_isend_irecv(ops):
-            req.wait()
-    if back is not None:
-        recv.copy_(back)
-
-
-def _allreduce_sum(dist, group, t):
-    if dist.get_backend(group) == "gloo" and t.is_cuda:
-        h = t.cpu()
-        dist.all_reduce(h, op=dist.ReduceOp.SUM, group=group)
-        t.copy_(h)
-    else:
-        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
-
-
 def inpaint_nans_by_springs_sharded(A_band, img_rows, *, rank=None, world_size=None, group=None, ops=None,
-                                    atol=1e-6, btol=1e-6, conlim=1e8, iter_lim=-1, poll=8):
+                                    atol=1e-6, btol=1e-6, conlim=1e8, iter_lim=-1, poll=8, comm=None):
     """Spring infill (SciPy-LSQR semantics) of a raster split into row bands; ``A_band`` (this rank's
     rows, float64) is filled in place.  Returns ``(istop, itn, n_unknown)`` - equal on every rank.
 
@@ -457,38 +518,31 @@ def inpaint_nans_by_springs_sharded(A_band, img_rows, *, rank=None, world_size=N
     same iteration.  Summation order differs from one device (block partials per band), so
     values agree to ~1e-12 and ``itn`` is normally identical (hard part 1).
     """
-    import torch.distributed as dist
-    if world_size is None:
-        world_size = dist.get_world_size(group) if dist.is_initialized() else 1
-    if rank is None:
-        rank = dist.get_rank(group) if dist.is_initialized() else 0
+    if comm is None:
+        comm = BandComm(group, rank, world_size)
+    rank, world_size, multi = comm.rank, comm.world, comm.multi
     b0, b1 = band_rows(img_rows, world_size, rank)
     if A_band.shape[0] != b1 - b0:
         raise ValueError("band has %d rows, expected %d" % (A_band.shape[0], b1 - b0))
-    multi = world_size > 1
     if ops is None:
         ops = HipSpringsOps(A_band, rank > 0, rank < world_size - 1)
     n = ops.rows
 
-    def reduce():
+    def reduce(t=None):
         if multi:
-            _allreduce_sum(dist, group, ops.red)
-
-    def reduce2():
-        if multi:
-            _allreduce_sum(dist, group, ops.red2)
+            comm.all_reduce(ops.red if t is None else t)
 
     ops.begin(atol, btol, conlim, iter_lim)
     ops.phase(PH_MASK)
     if multi:
-        _shift(dist, group, rank, world_size, ops.hole[1], ops.hole[n + 1], up=True)
-        _shift(dist, group, rank, world_size, ops.A[0], ops.abelow, up=True)
+        comm.shift(ops.hole[1], ops.hole[n + 1], up=True)
+        comm.shift(ops.A[0], ops.abelow, up=True)
     reduce()
     ops.phase(PH_RHS)
     reduce()
     ops.phase(PH_BNORM)
     if multi:
-        _shift(dist, group, rank, world_size, ops.uv[n], ops.uv[0], up=False)
+        comm.shift(ops.uv[n], ops.uv[0], up=False)
     ops.phase(PH_ATU)
     reduce()
     ops.phase(PH_INIT_ALFA)
@@ -496,14 +550,14 @@ def inpaint_nans_by_springs_sharded(A_band, img_rows, *, rank=None, world_size=N
     while not done:
         for _ in range(poll):
             if multi:
-                _shift(dist, group, rank, world_size, ops.v[1], ops.v[n + 1], up=True)
+                comm.shift(ops.v[1], ops.v[n + 1], up=True)
             ops.phase(PH_AV)                                 # u_k = S v_{k-1} - alfa u_{k-1}
             reduce()
             ops.phase(PH_BETA_RHO)                           # beta_k; rho_k, t1_k, 1/rho_k need nothing else
             if multi:
-                _shift(dist, group, rank, world_size, ops.uv[n], ops.uv[0], up=False)
+                comm.shift(ops.uv[n], ops.uv[0], up=False)
             ops.phase(PH_ATUXW)                              # w_{k-1}, dk_k, (x_k every second k), v_k
-            reduce2()                                        # [|v|^2, |dk|^2] as one buffer
+            reduce(ops.red2)                                      # [|v|^2, |dk|^2] as one buffer
             ops.phase(PH_ALFA_TESTS)                         # alfa_k, rest of the rotation, stopping tests
         istop, itn, nunk, done = ops.status()
     if nunk > 0:
@@ -551,17 +605,8 @@ class HipPointOps:
         return _cloud.grid_rows(xd, yd, zd, inv, grid_shape, row0, rows_local, bin_type)
 
 
-def _a2a(dist, group, out, inp, out_splits, in_splits):
-    """all_to_all_single; gloo stages CUDA tensors through the host (rehearsals on a one-GPU box)"""
-    if dist.get_backend(group) == "gloo" and inp.is_cuda:
-        ho = out.cpu()
-        dist.all_to_all_single(ho, inp.cpu(), output_split_sizes=out_splits, input_split_sizes=in_splits, group=group)
-        out.copy_(ho)
-    else:
-        dist.all_to_all_single(out, inp, output_split_sizes=out_splits, input_split_sizes=in_splits, group=group)
-
-
-def create_dem_sharded(xd, yd, zd, cellsize=1, bin_type='max', *, rank=None, world_size=None, group=None, ops=None):
+def create_dem_sharded(xd, yd, zd, cellsize=1, bin_type='max', *, rank=None, world_size=None, group=None, ops=None,
+                       comm=None):
     """create_dem (neilpy/neilpy.py:1110-1166) with the POINTS sharded: every rank passes its own 1/N of the cloud
     and gets its row band of the raster - nothing is replicated (the all-to-all form).
 
@@ -576,34 +621,23 @@ def create_dem_sharded(xd, yd, zd, cellsize=1, bin_type='max', *, rank=None, wor
     ``b0:b1`` of the single-device raster: min / max do not depend on the order points arrive in.
     """
     import torch
-    import torch.distributed as dist
     from . import api
     from .affine import from_origin
-    if world_size is None:
-        world_size = dist.get_world_size(group) if dist.is_initialized() else 1
-    if rank is None:
-        rank = dist.get_rank(group) if dist.is_initialized() else 0
+    if comm is None:
+        comm = BandComm(group, rank, world_size)
+    rank, world_size, multi = comm.rank, comm.world, comm.multi
     if bin_type not in ('max', 'min'):
         raise ValueError('This type not supported.')                  # neilpy.py:1158
     if ops is None:
         ops = HipPointOps()
-    multi = world_size > 1
-    gloo = multi and dist.get_backend(group) == "gloo"
     xmin, xmax, ymin, ymax = ops.extent(xd, yd)
     # A rank whose extent is undefined (a NaN / inf coordinate, or no points) must stop EVERY rank.  MIN does not carry
     # a NaN reliably (RCCL's float min is fmin-like and drops it, gloo's std::min keeps it or not by operand order), so
     # the ranks agree on an explicit count of bad extents first and only reduce finite values.
-    bad = int(not np.isfinite([xmin, xmax, ymin, ymax]).all())
-    if multi:
-        nb = torch.tensor([bad], dtype=torch.int32, device="cpu" if gloo else xd.device)
-        dist.all_reduce(nb, op=dist.ReduceOp.SUM, group=group)
-        bad = int(nb.item())
-    if bad:
+    if comm.reduced(int(not np.isfinite([xmin, xmax, ymin, ymax]).all()), torch.int32, "SUM", xd.device):
         raise ValueError("zero-size or non-finite point set: the raster's extent is undefined")
-    if multi:
-        e = torch.tensor([xmin, ymin, -xmax, -ymax], dtype=torch.float64, device="cpu" if gloo else xd.device)
-        dist.all_reduce(e, op=dist.ReduceOp.MIN, group=group)
-        xmin, ymin, xmax, ymax = float(e[0]), float(e[1]), -float(e[2]), -float(e[3])
+    e = comm.reduced([xmin, ymin, -xmax, -ymax], torch.float64, "MIN", xd.device)
+    xmin, ymin, xmax, ymax = e[0], e[1], -e[2], -e[3]
     xedges, yedges = api._edges_from_extent(np.float64(xmin), np.float64(xmax), np.float64(ymin), np.float64(ymax), cellsize)
     nx, ny = len(xedges) - 1, len(yedges) - 1
     t = from_origin(xedges[0], yedges[0], cellsize, cellsize)
@@ -613,22 +647,18 @@ def create_dem_sharded(xd, yd, zd, cellsize=1, bin_type='max', *, rank=None, wor
     b0, b1 = band_rows(ny, world_size, rank)
     if multi:
         counts, sx, sy, sz = ops.bucket(xd, yd, zd, inv, ny, world_size)
-        cnt = counts.cpu() if (gloo or not counts.is_cuda) else counts
+        cnt = counts.cpu() if comm.gloo else counts
         got = torch.empty_like(cnt)
-        dist.all_to_all_single(got, cnt, group=group)                  # how many points every rank sends me
+        comm.all_to_all(got, cnt)                                      # how many points every rank sends me
         in_splits = [int(v) for v in counts.cpu().tolist()]
         out_splits = [int(v) for v in got.cpu().tolist()]
         n_in = sum(out_splits)
         rx, ry, rz = (torch.empty(n_in, dtype=torch.float64, device=xd.device) for _ in range(3))
         for dst_t, src_t in ((rx, sx), (ry, sy), (rz, sz)):
-            _a2a(dist, group, dst_t, src_t, out_splits, in_splits)
+            comm.all_to_all(dst_t, src_t, out_splits, in_splits)
         xd, yd, zd = rx, ry, rz
     band, empty, n_out = ops.bin_band(xd, yd, zd, inv, (ny, nx), b0, b1 - b0, bin_type)
-    if multi:
-        o = torch.tensor([n_out], dtype=torch.int64, device="cpu" if gloo else band.device)
-        dist.all_reduce(o, op=dist.ReduceOp.SUM, group=group)
-        n_out = int(o.item())
-    if n_out > 0:
+    if comm.reduced(int(n_out), torch.int64, "SUM", band.device) > 0:
         raise ValueError("invalid entry in coordinates array")       # np.ravel_multi_index, neilpy.py:1151
     return band, empty, t, (ny, nx), (b0, b1)
 
@@ -636,28 +666,9 @@ def create_dem_sharded(xd, yd, zd, cellsize=1, bin_type='max', *, rank=None, wor
 # ------------------------------------------------------------------------------------------
 # the whole smrf() over row bands
 # ------------------------------------------------------------------------------------------
-def _all_gather_rows(dist, group, part, sizes):
-    """Concatenate every rank's leading-dimension block (``sizes[k]`` rows on rank k) on every rank.
-    Blocks are padded to the largest one (all_gather wants equal shapes); gloo stages CUDA tensors
-    through the host."""
-    import torch
-    world = len(sizes)
-    if world == 1:
-        return part
-    pad = max(sizes)
-    buf = torch.zeros((pad,) + tuple(part.shape[1:]), dtype=part.dtype, device=part.device)
-    buf[:part.shape[0]].copy_(part)
-    staged = dist.get_backend(group) == "gloo" and part.is_cuda
-    src = buf.cpu() if staged else buf
-    outs = [torch.empty_like(src) for _ in range(world)]
-    dist.all_gather(outs, src, group=group)
-    full = torch.cat([o[:n] for o, n in zip(outs, sizes)], dim=0)
-    return full.to(part.device) if staged else full
-
-
 def smrf_sharded(x, y, z, cellsize=1, windows=5, slope_threshold=.15, elevation_threshold=.5, elevation_scaler=1.25,
                  low_filter_slope=5, low_outlier_fill=False, *, rank=None, world_size=None, group=None,
-                 points="replicated"):
+                 points="replicated", comm=None):
     """neilpy.smrf (neilpy/neilpy.py:1685-1808) with the raster split into row bands, one rank per GPU.
 
     ``points="replicated"``: every rank passes the FULL point set (or reads it from the same file) and bins it
@@ -675,12 +686,10 @@ def smrf_sharded(x, y, z, cellsize=1, windows=5, slope_threshold=.15, elevation_
     ALL points, the same on every rank (replicated), or of the rank's own points (sharded).
     """
     import torch
-    import torch.distributed as dist
     from . import api
-    if world_size is None:
-        world_size = dist.get_world_size(group) if dist.is_initialized() else 1
-    if rank is None:
-        rank = dist.get_rank(group) if dist.is_initialized() else 0
+    if comm is None:
+        comm = BandComm(group, rank, world_size)
+    rank, world_size = comm.rank, comm.world
     if np.isscalar(windows):
         windows = np.arange(windows) + 1
     windows = np.asarray(windows)
@@ -689,8 +698,7 @@ def smrf_sharded(x, y, z, cellsize=1, windows=5, slope_threshold=.15, elevation_
         raise ValueError("points must be 'replicated' or 'sharded'")
     xd, yd, zd = api._points_to_device(x, y, z)
     if points == "sharded":
-        band, empty, t, (ny, nx), (b0, b1) = create_dem_sharded(xd, yd, zd, cellsize, 'min', rank=rank,
-                                                                world_size=world_size, group=group)   # :1741
+        band, empty, t, (ny, nx), (b0, b1) = create_dem_sharded(xd, yd, zd, cellsize, 'min', comm=comm)        # :1741
     else:
         xedges, yedges = api._dem_edges(xd, yd, cellsize)                          # :1117-1124, same on every rank
         nx, ny = len(xedges) - 1, len(yedges) - 1
@@ -701,41 +709,32 @@ def smrf_sharded(x, y, z, cellsize=1, windows=5, slope_threshold=.15, elevation_
                                              bin_type='min')                       # :1741
         if n_out > 0:
             raise ValueError("invalid entry in coordinates array")
-    stats = {"inpaint1": inpaint_nans_by_springs_sharded(band, ny, rank=rank, world_size=world_size, group=group)}
+    stats = {"inpaint1": inpaint_nans_by_springs_sharded(band, ny, comm=comm)}
     neg = torch.empty_like(band)
     _lib.check(lib.smrf_negate_f64(_ptr(band), _ptr(neg), band.numel(), _stream()))
     low, _ = progressive_filter_sharded(neg, ny, np.array([1]), low_filter_slope * (np.array([1]) * cellsize),
-                                        rank=rank, world_size=world_size, group=group)                 # :1744
+                                        comm=comm)                                 # :1744
     low = low.clone()
     del neg
     if low_outlier_fill:                                                           # :1747-1749
         _lib.check(lib.smrf_mask_apply_f64(_ptr(band), _ptr(low), None, None, None, band.numel(), _stream()))
-        stats["inpaint1b"] = inpaint_nans_by_springs_sharded(band, ny, rank=rank, world_size=world_size, group=group)
-    obj, _ = progressive_filter_sharded(band, ny, windows, slope_threshold * (windows * cellsize), rank=rank,
-                                        world_size=world_size, group=group)        # :1752-1755
+        stats["inpaint1b"] = inpaint_nans_by_springs_sharded(band, ny, comm=comm)
+    obj, _ = progressive_filter_sharded(band, ny, windows, slope_threshold * (windows * cellsize), comm=comm)   # :1752-1755
     obj = obj.contiguous()
     object_cells = torch.empty_like(obj)
     _lib.check(lib.smrf_mask_apply_f64(_ptr(band), _ptr(empty), _ptr(low), _ptr(obj), _ptr(object_cells), band.numel(),
                                        _stream()))                                 # :1762-1763
-    stats["inpaint2"] = inpaint_nans_by_springs_sharded(band, ny, rank=rank, world_size=world_size, group=group)  # :1764
+    stats["inpaint2"] = inpaint_nans_by_springs_sharded(band, ny, comm=comm)       # :1764
     # tail: the spline needs the whole DTM; the points are split evenly
-    sizes = [band_rows(ny, world_size, k)[1] - band_rows(ny, world_size, k)[0] for k in range(world_size)]
-    Zpro = _all_gather_rows(dist, group, band, sizes)
+    Zpro = comm.all_gather_rows(band, band_sizes(ny, world_size))
     npts = xd.numel()
-    if points == "sharded":                                  # every rank classifies its own points, nothing to gather
-        if npts:
-            flags = api._classify_points_device(Zpro, t, cellsize, xd, yd, zd, elevation_threshold, elevation_scaler)[2]
-        else:
-            flags = torch.empty(0, dtype=torch.uint8, device=xd.device)
-        api.last_stats["sharded"] = stats
-        return band, t, object_cells.bool(), flags.bool(), (b0, b1)
-    psz = [band_rows(npts, world_size, k)[1] - band_rows(npts, world_size, k)[0] for k in range(world_size)]
-    p0, p1 = band_rows(npts, world_size, rank)
+    p0, p1 = (0, npts) if points == "sharded" else band_rows(npts, world_size, rank)    # sharded: the rank's own points
     if p1 > p0:
-        part = api._classify_points_device(Zpro, t, cellsize, xd[p0:p1].contiguous(), yd[p0:p1].contiguous(),
-                                           zd[p0:p1].contiguous(), elevation_threshold, elevation_scaler)[2]
+        flags = api._classify_points_device(Zpro, t, cellsize, xd[p0:p1].contiguous(), yd[p0:p1].contiguous(),
+                                            zd[p0:p1].contiguous(), elevation_threshold, elevation_scaler)[2]
     else:
-        part = torch.empty(0, dtype=torch.uint8, device=xd.device)
-    flags = _all_gather_rows(dist, group, part, psz)
+        flags = torch.empty(0, dtype=torch.uint8, device=xd.device)
+    if points == "replicated":
+        flags = comm.all_gather_rows(flags, band_sizes(npts, world_size))
     api.last_stats["sharded"] = stats
     return band, t, object_cells.bool(), flags.bool(), (b0, b1)

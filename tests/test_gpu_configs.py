@@ -164,51 +164,17 @@ def test_cfg4_sharded_driver_windows_1_to_50(nz, gpu_device):
     12-group exchange schedule 8 ranks run.  One rank after the other on this GPU; a neighbour's message is
     replaced by the same rows of the surface entering the group, computed on the whole raster."""
     import torch
-    from neilpy_amd import sharded
+    from sharded_one_gpu import run_bands
     N, world = 16384, 8
     Z = torch.from_numpy(nz.synth_dem(N, seed=20240)).to(gpu_device)
     win = np.arange(1, 51)
-    thr = .15 * (win * 1)
     want = nz.progressive_filter(Z, win, 1, .15)
     assert int(want.sum()) == 51388194                         # the headline result (test_gpu_fullsize pins it too)
-    groups = sharded.window_groups([int(w) for w in win], N // world)
+    # only the halo rows of the 12 surfaces entering the groups are kept in there (1 GiB per whole surface)
+    mask, _, groups = run_bands(nz, Z, win, world)
     assert len(groups) == 12
     assert sorted(i for g in groups for i in g) == list(range(50))
     for g in groups:
         assert sum(2 * int(win[i]) for i in g) <= max(256, (N // world) // 16) or len(g) == 1
-    # the surface entering each group: kept only for the group being checked to bound memory (1 GiB each)
-    real = sharded._exchange
-    masks = [None] * world
-    try:
-        # run all ranks group-synchronously is not possible with the driver's loop, so keep the 12 surfaces' halo rows
-        # only: rows within Sum(2r) of every band border
-        halo = {}
-        last = Z
-        for gi, grp in enumerate(groups):
-            m = sum(2 * int(win[i]) for i in grp)
-            for k in range(world):
-                b0, b1 = sharded.band_rows(N, world, k)
-                if k > 0:
-                    halo[(gi, k, "up")] = last[b0 - m:b0].clone()
-                if k < world - 1:
-                    halo[(gi, k, "down")] = last[b1:b1 + m].clone()
-            for i in grp:
-                last = nz.opening(last, radius=int(win[i]))
-        del last
-        for k in range(world):
-            b0, b1 = sharded.band_rows(N, world, k)
-            calls = []
-
-            def fake_exchange(dist, group, rank, world_size, send_up, recv_up, send_down, recv_down):
-                gi = len(calls)
-                calls.append(send_up.shape[0])
-                if recv_up is not None:
-                    recv_up.copy_(halo[(gi, k, "up")])
-                if recv_down is not None:
-                    recv_down.copy_(halo[(gi, k, "down")])
-            sharded._exchange = fake_exchange
-            mask, _ = sharded.progressive_filter_sharded(Z[b0:b1], N, win, thr, rank=k, world_size=world)
-            assert calls == [sum(2 * int(win[i]) for i in g) for g in groups]
-            assert torch.equal(mask.bool(), want[b0:b1]), k
-    finally:
-        sharded._exchange = real
+    for k in range(world):
+        assert torch.equal(mask[k * 2048:(k + 1) * 2048], want[k * 2048:(k + 1) * 2048]), k

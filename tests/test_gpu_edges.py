@@ -127,51 +127,27 @@ def test_sharded_driver_bands_on_one_gpu(nz, orc, gpu_device, world, shape, wind
     against the oracle."""
     import torch
     from neilpy_amd import sharded
+    from sharded_one_gpu import run_bands
     rng = np.random.default_rng(world * 100 + shape[0])
     Z = nz.synth_dem(shape[1], seed=9, rows=shape[0]).astype(np.float32)
     if with_nan:
         Z[rng.random(shape) < .02] = np.nan
         Z[shape[0] // world - 1, 5:40] = np.nan                       # a run of NaNs on a band's last row
     win = np.asarray(windows)
-    thr = .15 * (win * 1)
     want_m, want_w = orc.progressive_filter(Z, win, 1, .15, return_when_dropped=True)
-    Zd = torch.from_numpy(Z).to(gpu_device)
-    min_band = min(sharded.band_rows(shape[0], world, k)[1] - sharded.band_rows(shape[0], world, k)[0] for k in range(world))
-    groups = sharded.window_groups([int(w) for w in win], min_band, budget)
-    entering, last = [], Zd
-    for grp in groups:
-        entering.append(last)
-        for i in grp:
-            last = nz.opening(last, radius=int(win[i]))
-    real = sharded._exchange
-    try:
-        for k in range(world):
-            b0, b1 = sharded.band_rows(shape[0], world, k)
-            calls = []
 
-            def fake_exchange(dist, group, rank, world_size, send_up, recv_up, send_down, recv_down):
-                src = entering[len(calls)]
-                calls.append(send_up.shape[0])
-                # what this rank sends must be what the whole-raster surface holds in those rows (NaNs compare equal)
-                assert torch.equal(torch.nan_to_num(send_up, nan=-7.0), torch.nan_to_num(src[b0:b0 + send_up.shape[0]], nan=-7.0))
-                assert torch.equal(torch.nan_to_num(send_down, nan=-7.0), torch.nan_to_num(src[b1 - send_down.shape[0]:b1], nan=-7.0))
-                if recv_up is not None:
-                    recv_up.copy_(src[b0 - recv_up.shape[0]:b0])
-                if recv_down is not None:
-                    recv_down.copy_(src[b1:b1 + recv_down.shape[0]])
-            sharded._exchange = fake_exchange
-            ops = sharded.HipBandOps()
-            if with_nan:
-                ops.has_nan = lambda band: True                           # the all-reduced flag of a real run
-            mask, when = sharded.progressive_filter_sharded(Zd[b0:b1].contiguous(), shape[0], win, thr, rank=k, world_size=world,
-                                                            ops=ops, return_when_dropped=True, halo_budget=budget,
-                                                            overlap=(k % 2 == 0))       # both forms of the driver
-            torch.cuda.synchronize()
-            assert calls == [sum(2 * int(win[i]) for i in g) for g in groups]
-            assert np.array_equal(mask.cpu().numpy().astype(bool), want_m[b0:b1]), (k, "mask")
-            assert np.array_equal(when.cpu().numpy(), want_w[b0:b1]), (k, "when")
-    finally:
-        sharded._exchange = real
+    def band_ops():
+        ops = sharded.HipBandOps()
+        if with_nan:
+            ops.has_nan = lambda band: True                               # the all-reduced flag of a real run
+        return ops
+    # what every rank sends must be what the whole-raster surface holds in those rows: run_bands checks it
+    mask, when, _ = run_bands(nz, torch.from_numpy(Z).to(gpu_device), win, world, return_when_dropped=True, budget=budget,
+                              ops=band_ops, overlap=lambda k: k % 2 == 0)       # both forms of the driver
+    for k in range(world):
+        b0, b1 = sharded.band_rows(shape[0], world, k)
+        assert np.array_equal(mask[b0:b1].cpu().numpy(), want_m[b0:b1]), (k, "mask")
+        assert np.array_equal(when[b0:b1].cpu().numpy(), want_w[b0:b1]), (k, "when")
 
 
 @pytest.mark.parametrize("nbands", [1, 3, 8, 64])

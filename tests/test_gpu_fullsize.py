@@ -85,37 +85,13 @@ def test_cfg4_sharded_driver_equals_single_device(nz, Z4):
     The neighbour exchange is replaced by copying the same rows out of the surface that enters each group
     of windows (computed on the whole raster), which is what the neighbours would send."""
     import torch
-    from neilpy_amd import sharded
+    from sharded_one_gpu import run_bands
     win = np.arange(1, 19)                                     # groups (1..15), (16..18) on 2048-row bands
-    thr = .15 * (win * 1)
     want = nz.progressive_filter(Z4, win, 1, .15)
-    world = 8
-    groups = sharded.window_groups([int(w) for w in win], N4 // world)
+    mask, _, groups = run_bands(nz, Z4, win, 8)                # one exchange per group, sum(2r) rows: checked in there
     assert [len(g) for g in groups] == [15, 3]
-    entering, last = [], Z4                                    # the surface each group starts from
-    for grp in groups:
-        entering.append(last)
-        for i in grp:
-            last = nz.opening(last, radius=int(win[i]))
-    real = sharded._exchange
-    try:
-        for k in range(world):
-            b0, b1 = sharded.band_rows(N4, world, k)
-            calls = []
-
-            def fake_exchange(dist, group, rank, world_size, send_up, recv_up, send_down, recv_down):
-                src = entering[len(calls)]
-                calls.append(send_up.shape[0])
-                if recv_up is not None:
-                    recv_up.copy_(src[b0 - recv_up.shape[0]:b0])
-                if recv_down is not None:
-                    recv_down.copy_(src[b1:b1 + recv_down.shape[0]])
-            sharded._exchange = fake_exchange
-            mask, _ = sharded.progressive_filter_sharded(Z4[b0:b1], N4, win, thr, rank=k, world_size=world)
-            assert calls == [sum(2 * int(win[i]) for i in g) for g in groups]      # one exchange per group, sum(2r) rows
-            assert torch.equal(mask.bool(), want[b0:b1]), k
-    finally:
-        sharded._exchange = real
+    for k in range(8):
+        assert torch.equal(mask[k * 2048:(k + 1) * 2048], want[k * 2048:(k + 1) * 2048]), k
 
 
 def test_cfg2_full_call_vs_direct_kernel_chain(nz, gpu_device):

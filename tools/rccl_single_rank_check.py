@@ -37,7 +37,7 @@ g1, _e, t1 = sharded.create_dem_sharded(x, y, z, 1.0, "min", rank=0, world_size=
 g0, t0 = neilpy_amd.create_dem(x, y, z, 1.0, "min")
 print("create_dem_sharded equal", bool(torch.equal(torch.nan_to_num(g1, nan=-1.0), torch.nan_to_num(g0, nan=-1.0))), tuple(t1)[:6] == tuple(t0)[:6])
 # the halo exchange's own primitive - batch_isend_irecv of row blocks of a raster - with this rank as its own neighbour (RCCL
-# runs a send and the matching recv of one rank inside a group call as a device copy): the P2P path of sharded._exchange
+# runs a send and the matching recv of one rank inside a group call as a device copy): the P2P path of sharded.BandComm.sendrecv
 last = torch.arange(64 * 1024, dtype=torch.float32, device=dev).reshape(64, 1024)
 recv = torch.zeros((8, 1024), dtype=torch.float32, device=dev)
 ops = [dist.P2POp(dist.isend, last[10:18], 0), dist.P2POp(dist.irecv, recv, 0)]
