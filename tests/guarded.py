@@ -24,6 +24,8 @@ What a test then asks of the harness:
 ``g.owns(t)``         ``t``'s storage is one of the arenas;
 ``g.unchanged(t)``    ``t`` has the bytes of its snapshot (NaN payloads and zero signs included); ``where=`` restricts
                       the comparison to the elements of a boolean mask (entry points that fill a raster in place);
+``before_fill=``      (optional, also settable as ``g.before_fill``) a callable run on the current stream before each
+                      arena's poison fill; tests/streamed.py enqueues a delay there.  Absent, nothing changes.
 ``same_bits(a, b)``   two NumPy results agree byte for byte - the comparison of a run under poison 0xFF (NaN in every
                       float type, 255 in uint8) with a run under 0x5A (an ordinary finite number in every float type):
                       a cell nobody wrote, or one computed from memory nobody wrote, differs between the two.
@@ -73,10 +75,11 @@ def same_bits(a, b):
 
 
 class Guarded:
-    def __init__(self, device, poison):
+    def __init__(self, device, poison, before_fill=None):
         self.device = self._resolve(device)
         self.poison = int(poison)
         assert 0 <= self.poison <= 255
+        self.before_fill = before_fill                # tests/streamed.py: called on the current stream ahead of every poison fill
         self.arenas = []
 
     # ------------------------------------------------------------------ allocation
@@ -107,6 +110,8 @@ class Guarded:
             n *= v
         a = _Arena()
         a.nbytes = n * _ORIG["empty"](0, dtype=dtype).element_size()
+        if self.before_fill is not None:
+            self.before_fill()
         a.buf = _ORIG["full"]((GUARD + a.nbytes + GUARD,), self.poison, dtype=torch.uint8, device=self.device)
         a.dtype, a.shape, a.site, a.snap = dtype, shape, _call_site(), None
         self.arenas.append(a)
@@ -237,7 +242,7 @@ class Guarded:
 
 
 @contextlib.contextmanager
-def guarded(device, poison):
-    g = Guarded(device, poison)
+def guarded(device, poison, before_fill=None):
+    g = Guarded(device, poison, before_fill)
     with g:
         yield g

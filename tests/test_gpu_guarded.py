@@ -394,11 +394,27 @@ def test_raster_stats(gpu_device, dtype):
                     reference=lambda got: (got.dtype == X.dtype and got == rn.rmse(X)) or pytest.fail("rmse %r" % (ctx,)))
 
 
+def brassel_reference(Hs, Z, kw, ctx):
+    """tests/test_gpu_relief.py's comparison of brassel_atmospheric_perspective on a result in hand"""
+    from test_gpu_relief import BRASSEL_MARGIN
+
+    def ref(got):
+        with np.errstate(all='ignore'):
+            v, was_int = rn.brassel_value(Hs, Z, **kw)
+            want = rn.brassel_atmospheric_perspective(Hs, Z, **kw)
+        assert got.dtype == want.dtype == (np.uint8 if was_int else np.float64) and got.shape == want.shape, kw
+        if not was_int:
+            return assert_close(got, want, 1.0, (kw, Z.dtype, Hs.dtype))
+        with np.errstate(all='ignore'):
+            ok = ~(np.abs(255 * v - (np.floor(255 * v) + 0.5)) < BRASSEL_MARGIN)
+        assert np.array_equal(got[ok], want[ok]), (ctx, int((got[ok] != want[ok]).sum()))
+    return ref
+
+
 @pytest.mark.parametrize("dtype", [F32, F64])
 def test_relief_images(gpu_device, dtype):
     """normalize with a median knot, the colour gather against the device's own shade, brassel with uint8 and float shades"""
     import neilpy_amd as na
-    from test_gpu_relief import BRASSEL_MARGIN
     G = golden("relief.npz")
     for Z, ctx in cases_of(GRADIENT_SHAPES, (dtype,)):
         xr, yr = ['min', 'median', 'max'], [-1, 0, 1]
@@ -419,17 +435,7 @@ def test_relief_images(gpu_device, dtype):
         h = rng.uniform(0, 1, size=Z.shape)
         for hkind, Hs in (("u8", np.round(255 * h).astype(np.uint8)), ("f32", h.astype(F32)), ("f64", h)):
             kw = dict(k=2.303, C2=0.41) if hkind != "f32" else dict(k=1.371, flat=200, reverse=True)
-
-            def ref(got, Hs=Hs, kw=kw, hkind=hkind):
-                with np.errstate(all='ignore'):
-                    v, was_int = rn.brassel_value(Hs, Z, **kw)
-                    want = rn.brassel_atmospheric_perspective(Hs, Z, **kw)
-                assert got.dtype == want.dtype == (np.uint8 if was_int else np.float64) and got.shape == want.shape, kw
-                if not was_int:
-                    return assert_close(got, want, 1.0, (kw, Z.dtype, Hs.dtype))
-                with np.errstate(all='ignore'):
-                    ok = ~(np.abs(255 * v - (np.floor(255 * v) + 0.5)) < BRASSEL_MARGIN)
-                assert np.array_equal(got[ok], want[ok]), (ctx, hkind, int((got[ok] != want[ok]).sum()))
+            ref = brassel_reference(Hs, Z, kw, (ctx, hkind))
             run_guarded(lambda Ht, Zt: F("brassel_atmospheric_perspective")(Ht, Zt, **kw), [Hs, Z],
                         name="brassel_atmospheric_perspective", ctx=(ctx, hkind), reference=ref)
 
@@ -569,15 +575,20 @@ def test_create_dem_second_trip(gpu_device):
                 reference=lambda got: dem_match(got, want, "second trip"))
 
 
-def test_read_las_xyz(gpu_device):
+def read_las_case():
+    """run_guarded's arguments for read_las_xyz on the smallest golden file (shared with tests/test_gpu_streams.py)"""
     from test_las import CASES, LAS
     tag = min(CASES, key=lambda c: LAS[c + "_col_x"].size)
 
     def ref(got):
         for k, c in enumerate("xyz"):
             assert np.array_equal(got[k], LAS[tag + "_col_" + c]), (tag, c)          # bit-exact with the reference's floats
-    run_guarded(lambda: F("read_las_xyz")(os.path.join(GOLDEN, "las", tag + ".las"))[1:], [], name="read_las_xyz", ctx=tag,
-                reference=ref)
+    return dict(fn=lambda: F("read_las_xyz")(os.path.join(GOLDEN, "las", tag + ".las"))[1:], inputs=[], name="read_las_xyz",
+                ctx=tag, reference=ref)
+
+
+def test_read_las_xyz(gpu_device):
+    run_guarded(**read_las_case())
 
 
 # ------------------------------------------------------------------------------------------
@@ -615,6 +626,11 @@ def test_inpaint_nearest(gpu_device, dtype):
 def test_inpaint_springs(gpu_device, shape, seed, share):
     """through the public function, in place: tests/test_gpu_springs.py's rasters, stop and bar (1000 x how far the oracle's
     own answer moves when every sum is taken in another order, never above 1e-7); the known cells keep their bits"""
+    run_guarded(**springs_case(shape, seed, share))
+
+
+def springs_case(shape, seed, share):
+    """run_guarded's arguments for test_inpaint_springs (shared with tests/test_gpu_streams.py)"""
     import neilpy_amd as na
     from oracle import smrf_oracle as orc
     from test_gpu_springs import oracle_run, raster as springs_raster
@@ -636,11 +652,16 @@ def test_inpaint_springs(gpu_device, shape, seed, share):
         diff = float(np.abs(got - want)[hole].max())
         print("springs %s: device vs oracle %.3g, bar %.3g" % (shape, diff, bar))
         assert not np.isnan(got).any() and diff <= bar, (diff, bar)
-    run_guarded(fill, [A], name="inpaint_nans_by_springs", ctx=shape, known=lambda i, a: ~np.isnan(a), reference=ref,
+    return dict(fn=fill, inputs=[A], name="inpaint_nans_by_springs", ctx=shape, known=lambda i, a: ~np.isnan(a), reference=ref,
                 after=exact_workspace(lib().smrf_springs_workspace_bytes(*shape)))
 
 
 def test_inpaint_fda(gpu_device):
+    run_guarded(**fda_case())
+
+
+def fda_case():
+    """run_guarded's arguments for test_inpaint_fda (shared with tests/test_gpu_streams.py)"""
     import neilpy_amd as na
     from test_fda import CASES, G, RTOL, _close_stop
     tag = min((c for c in CASES if np.isnan(G[c + "_in"]).any() and not np.isnan(G[c + "_in"]).all()),
@@ -656,7 +677,7 @@ def test_inpaint_fda(gpu_device):
     def ref(got):
         scale = max(1.0, float(np.nanmax(np.abs(want))))
         assert got.dtype == np.float64 and np.max(np.abs(got - want)) <= RTOL * scale, tag
-    run_guarded(fill, [A], name="inpaint_nans_by_fda", ctx=tag, known=lambda i, a: ~np.isnan(a), reference=ref,
+    return dict(fn=fill, inputs=[A], name="inpaint_nans_by_fda", ctx=tag, known=lambda i, a: ~np.isnan(a), reference=ref,
                 after=exact_workspace(lib().smrf_fda_workspace_bytes(*A.shape)))
 
 
@@ -745,10 +766,14 @@ def test_spline(gpu_device, shape):
     """smrf_spline_solve_ws_f64 and smrf_spline_eval_f64 as smrf() calls them, the scratch plane poisoned, against SciPy
     with the bars of tests/test_gpu_parity.py's test_spline_matches_scipy.  (300, 257): two chunks on both axes and a last
     64-column tile one column wide."""
+    run_guarded(**spline_case(shape))
+
+
+def spline_case(shape):
+    """run_guarded's arguments for test_spline (shared with tests/test_gpu_streams.py)"""
     import torch
     from scipy import interpolate
     from neilpy_amd import _lib, spline
-    L = lib()
     rows, cols = shape
     rng = np.random.default_rng(12)
     Z = rng.normal(100, 5, shape)
@@ -760,6 +785,7 @@ def test_spline(gpu_device, shape):
     (tx, lur), (ty, luc) = spline.axis_factors(rows), spline.axis_factors(cols)
 
     def call(coef, txd, tyd, lurd, lucd, prd, pcd):
+        L = lib()                                       # at call time: tests/streamed.py records through what load() returns
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         p = lambda t: C.c_void_p(t.data_ptr())          # noqa: E731
         scratch = torch.empty_like(coef)
@@ -774,7 +800,7 @@ def test_spline(gpu_device, shape):
         np.testing.assert_allclose(got[0].ravel(), f.tck[2], rtol=0, atol=1e-10)
         np.testing.assert_allclose(got[1], want, rtol=0, atol=1e-9)
     # the solve works in place on the coefficient plane: input 0 is exempt from "unchanged", the others are not
-    run_guarded(call, [Z, tx, ty, lur, luc, pr, pc], name="smrf_spline", ctx=shape, reference=ref,
+    return dict(fn=call, inputs=[Z, tx, ty, lur, luc, pr, pc], name="smrf_spline", ctx=shape, reference=ref,
                 known=lambda i, a: np.zeros(a.shape, bool) if i == 0 else None)
 
 
@@ -784,6 +810,15 @@ def test_spline(gpu_device, shape):
 def test_smrf_samp21(gpu_device):
     """smrf() with tensor inputs: every intermediate plane of the pipeline behind guards at once; against the golden of
     tests/test_gpu_parity.py's test_smrf_samples_golden, through that file's check_smrf"""
+    case, tails = smrf_case()
+    run_guarded(**case)
+    assert same_bits(tails[0]["elevation_values"], tails[1]["elevation_values"])
+    assert same_bits(tails[0]["slope_values"], tails[1]["slope_values"])
+
+
+def smrf_case():
+    """run_guarded's arguments for test_smrf_samp21 and the list that gets each run's tail statistics (shared with
+    tests/test_gpu_streams.py)"""
     import neilpy_amd as na
     from test_gpu_parity import META, check_smrf
     x, y, z, g = load_sample("samp21")
@@ -806,9 +841,7 @@ def test_smrf_samp21(gpu_device):
                 return got
         pts = check_smrf(Shim, gold, x, y, z, kw, "samp21" in META["full_dtm"], META["stride"])
         assert abs(100.0 * (1.0 - np.mean(pts == g)) - META["anchors"]["samp21"]["total_error_pct"]) < 1e-9
-    run_guarded(call, [x, y, z], name="smrf", ctx="samp21", reference=ref)
-    assert same_bits(tails[0]["elevation_values"], tails[1]["elevation_values"])
-    assert same_bits(tails[0]["slope_values"], tails[1]["slope_values"])
+    return dict(fn=call, inputs=[x, y, z], name="smrf", ctx="samp21", reference=ref), tails
 
 
 # ------------------------------------------------------------------------------------------
@@ -817,6 +850,11 @@ def test_smrf_samp21(gpu_device):
 def test_sharded_bands_on_one_gpu(gpu_device):
     """tests/test_gpu_edges.py's test_sharded_driver_bands_on_one_gpu at its smallest parametrisation (2 ranks, 200 x 131,
     windows 2, 6, 1), every rank in turn in this process: band planes and halo buffers come from sharded.py"""
+    run_guarded(**sharded_case())
+
+
+def sharded_case():
+    """run_guarded's arguments for test_sharded_bands_on_one_gpu (shared with tests/test_gpu_streams.py)"""
     import neilpy_amd as na
     from neilpy_amd import sharded
     from oracle import smrf_oracle as orc
@@ -829,7 +867,7 @@ def test_sharded_bands_on_one_gpu(gpu_device):
         mask, when, _ = run_bands(na, Zt, win, world, return_when_dropped=True, budget=None, ops=sharded.HipBandOps,
                                   overlap=lambda k: k % 2 == 0)
         return mask, when
-    run_guarded(call, [Z], name="sharded", ctx=shape,
+    return dict(fn=call, inputs=[Z], name="sharded", ctx=shape,
                 reference=lambda got: (np.array_equal(got[0], want_m) and np.array_equal(got[1], want_w)) or pytest.fail("sharded"))
 
 
