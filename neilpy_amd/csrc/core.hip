@@ -29,6 +29,7 @@ SmrfSwitches read_switches() {
   s.chain_rounds = env_int("SMRF_CHAIN_ROUNDS", 3);
   s.ring_debug = env_int("SMRF_RING_DEBUG", 0);
   s.ero_inc = env_int("SMRF_ERO_INC", 1);
+  s.dil_cross = env_int("SMRF_DIL_CROSS", 1);
   return s;
 }
 // Read ONCE, at library load: a process that sets SMRF_* after importing neilpy_amd changes nothing until it calls

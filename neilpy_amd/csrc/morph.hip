@@ -190,6 +190,20 @@ int dilate_flag_api(const T* eroded, const T* last, T* opened, uint8_t* mask, ui
   return disk_filter(a, true, impl, (hipStream_t)stream);
 }
 
+// the dilation + flag step of a rim-free window on a whole raster without NaN, from e_{R-1}: the 5-point cross of the erosion is
+// taken on load (morph_ring.h, ring_cross_kernel; the radii of smrf_dil_cross_has)
+int dilate_cross_flag_f32(const float* e_prev, const float* last, float* opened, uint8_t* mask, uint8_t* when, double thr, int widx,
+                          int rows, int cols, int radius, hipStream_t stream) {
+  if (!smrf_dil_cross_has(4, radius)) return smrf_fail(SMRF_E_UNSUPPORTED, "no cross-on-load dilation for radius %d", radius);
+  DiskArgs<float> a{};
+  a.in = e_prev; a.out = opened; a.last = last; a.mask = mask; a.when = when; a.thr = thr; a.thr_lo = smrf_float_below(thr); a.widx = widx;
+  set_band(a, rows, cols, cols, 0, rows, 0, rows);
+  a.radius = radius;
+  if (int rc = check_band(a)) return rc;
+  a.seg = smrf_sw().ring_seg;
+  return RingFn<float>::call(a, SMRF_RING_DILATE_CROSS, stream);
+}
+
 template <typename T>
 int count_nan_api(const T* p, int64_t n, int64_t* h_count, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
@@ -272,7 +286,8 @@ int progressive_filter_api(const T* Z, int rows, int cols, const int32_t* window
   const size_t plane = (size_t)rows * cols;
   T* E = reinterpret_cast<T*>(ws);
   // Three planes whose roles rotate: pe holds the latest two-pass window's eroded surface, pl the surface `last` (-1: Z),
-  // and a launch writes its opened surface (the incremental erosion: its eroded one) into a plane that is neither.
+  // and a launch writes its opened surface (the incremental erosion: its eroded one) into a plane that is neither.  After a
+  // folded window (smrf_pf_fold) pe still holds the window BEFORE's eroded surface.
   T* P[3] = {E, E + plane, E + 2 * plane};
   int pe = 0, pl = -1;
   auto spare = [&]() { for (int k = 0; k < 3; ++k) if (k != pe && k != pl) return k; return 0; };
@@ -287,14 +302,16 @@ int progressive_filter_api(const T* Z, int rows, int cols, const int32_t* window
   // loop below executes that plan.  route / pattern: one call-local buffer; the incremental-erosion flags are what
   // smrf_pf_ero_inc_windows reports.
   const SmrfSwitches& sw = smrf_sw();
-  SmrfPfRules rules{(int)sizeof(T), sw.fused, sw.chain, sw.ero_inc, impl, nan_aware > 0, 0};
+  SmrfPfRules rules{(int)sizeof(T), sw.fused, sw.chain, sw.ero_inc, impl, nan_aware > 0, 0, sw.dil_cross};
   std::vector<int32_t> plan_buf((size_t)2 * nwin);
   int32_t* const route = plan_buf.data();
   int32_t* const pattern = route + nwin;
   g_ero_inc_taken.assign((size_t)nwin, 0);
+  std::vector<uint8_t> fold((size_t)nwin, 0);              // smrf_pf_fold: windows whose erosion is taken inside their dilation pass
   auto make_plan = [&](int with_nan) {
     rules.nan_aware = with_nan;
     smrf_pf_route(rules, windows, nwin, rows, (long long)plane, route, g_ero_inc_taken.data(), pattern);
+    smrf_pf_fold(rules, windows, route, g_ero_inc_taken.data(), nwin, fold.data());
   };
   make_plan(nan_aware > 0);
   // nan_aware < 0: the library finds out itself.  When the plan for a raster without NaN starts with a chained / table-free
@@ -383,7 +400,18 @@ int progressive_filter_api(const T* Z, int rows, int cols, const int32_t* window
         ++i;
         break;
       default:                   // two passes: ring or direct kernels by `impl`, the copy kernel for radius 0
-        if (g_ero_inc_taken[(size_t)i]) {
+        if (fold[(size_t)i] == kPfFoldCross) {
+          // a rim-free window (P_R empty: e_R = erode(e_{R-1}, cross)) launches no erosion: its dilation pass reads e_{R-1} from
+          // P[pe], takes the cross on load (morph_ring.h, ring_cross_kernel) and writes opened_R into the spare plane.  P[pe] keeps
+          // e_{R-1}: the next window cannot start from it (smrf_pf_fold, kPfFoldAfter) and erodes over it.
+          if constexpr (sizeof(T) == 4) {
+            if (int rc = dilate_cross_flag_f32(P[pe], last, opened, mask, when, thr[i], i, rows, cols, r, stream)) return rc;
+          } else {
+            return smrf_fail(SMRF_E_HIP, "internal: no cross on load at this dtype");
+          }
+          last = opened;
+          pl = po;
+        } else if (smrf_pf_runs_inc(g_ero_inc_taken.data(), fold.data(), i)) {
           // window R's erosion from window R-1's (morph_incero.h): e_R = min(erode(e_{R-1}, cross), min over the
           // leftover cells P_R of last).  e_R goes into the spare plane (it held opened_{R-2}), then opened_R goes over e_{R-1}
           if constexpr (sizeof(T) == 4) {

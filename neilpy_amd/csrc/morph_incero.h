@@ -27,6 +27,13 @@ namespace smrf {
 
 #include "ero_inc.inc"
 // (SMRF_INCERO_MIN_RADIUS / _MAX_RADIUS, the radii with an instance, and the adoption table ero_inc_adopt.inc: pf_route.h)
+// the radii pf_route.h folds into the dilation pass (cross on load) are exactly the rim-free ones from the first two-pass window up
+constexpr bool dil_cross_radii_are_rim_free() {
+  for (int r = SMRF_INCERO_MIN_RADIUS; r <= SMRF_INCERO_MAX_RADIUS; ++r)
+    if (smrf_dil_cross_has(4, r) != (kEroInc[r].n == 0)) return false;
+  return true;
+}
+static_assert(dil_cross_radii_are_rim_free(), "smrf_dil_cross_has (pf_route.h) against ero_inc.inc");
 
 // Two choices per radius, both made by measurement on MI355X at 16384^2 (profiles/incero_mirror.md sections 1 and 3):
 //   kIncEroPlanKind  how a batch's LDS reads are planned (IncEroCfg::make_plan).  The mirror plan with split groups everywhere;

@@ -1195,366 +1195,67 @@ __device__ __forceinline__ void ring_build_consume(typename Vec2<T>::type* const
   ring_consume<T, R, DIL, TW, NP>(L, par, tid, acc, outv);
 }
 
+// ring_cross_kernel's row pairs per batch and the waves per SIMD it is built for: the cells of the crosses (3 ROWS + 2 per position
+// instead of ROWS) are held from the prefetch to the end of the build phases, and every instance is to hold them in registers
+// (no scratch).  0 = the plain instance's.  Per radius (profiles/dil_cross.md); tuning builds override with -DSMRF_CROSS_NP(R)=..
+// and -DSMRF_CROSS_OCC(R)=..
+// Compiled for gfx950: R = 16 with the plain instance's 3 row pairs at 4 waves per SIMD spills 240 B, with 2 pairs at 3 waves it
+// takes 156 VGPRs; R = 21 (in place, 2 pairs) 44 B at 4 waves, 147 VGPRs at 3; R = 36 with 3 pairs at 3 waves 216 B, at 2 waves 230
+// VGPRs (with 1 pair 166 VGPRs at 3 waves, which measured 4.5 percent slower: 1.337 against 1.278 ms per window).
+#ifndef SMRF_CROSS_NP
+#define SMRF_CROSS_NP(R) ((R) == 16 ? 2 : 0)
+#endif
+#ifndef SMRF_CROSS_OCC
+#define SMRF_CROSS_OCC(R) ((R) == 36 ? 2 : 3)
+#endif
+template <int R, int TW, int NP>
+constexpr int ring_cross_occ() {
+  using C = RingCfg<float, R, TW, NP>;
+  constexpr int o = SMRF_CROSS_OCC(R) > 0 ? SMRF_CROSS_OCC(R) : C::OCC_REG;
+  return o < C::OCC_LDS ? o : C::OCC_LDS;
+}
+
+// The single-pass kernels.  Their body is ring_kernel_body.inc.  CROSS (ring_cross_kernel: the dilation of a rim-free window, fp32,
+// whole rasters without NaN): `in` is e_{R-1}, and what is staged as level 0 is erode(e_{R-1}, 5-point cross) = e_R (morph_incero.h:
+// P_R is empty) - per staged position and row the five cells min3(min3(c, l, r), up, down), rows at RowFold coordinates y - 1, y,
+// y + 1 and columns at smrf_fold(x +- 1) of the position's own folded column, as inc_erode_kernel's cross_loads takes them: the
+// period-2n reflect commutes with the cross (fold(fold(y) + 1) = fold(y -+ 1), and the cross is symmetric), so the cross of the
+// folded cell IS e_R there.  The own-column cells of a batch's neighbouring rows are shared: ROWS + 2 centre loads and 2 ROWS side
+// loads per position instead of ROWS loads.  Everything after staging is the plain instance's.
 template <typename T, int R, bool DIL, int TW, int NP>
 __global__ __launch_bounds__(TW, (RingCfg<T, R, TW, NP>::OCC))
 void ring_kernel(const DiskArgs<T> a) {
-  using C = RingCfg<T, R, TW, NP>;
-  using T2 = typename Vec2<T>::type;
-  constexpr int WP = C::WP, ROWS = C::ROWS, NLEV = C::NLEV;
-  // fp64 with three row pairs per batch is NOT a validated configuration: a variant build that forced it gave wrong cells at
-  // R = 57, 58, 62, 63, 64 (512 registers + 240-290 B of scratch per lane; tools/ab_equal.py, profiles/r05_f64_np.md) while
-  // every shipped instance (<= 2 pairs) equals the oracle on every radius.  ring_tune.inc's fp64 caps keep it out.
-  static_assert(sizeof(T) == 4 || NP <= 2, "fp64 ring instances are validated for at most two row pairs per batch");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smrf_lds[];
-  T2* const L = reinterpret_cast<T2*>(smrf_lds);         // [NP][NLEV][WP] of {row A, row B}
-
-  const int tid = threadIdx.x;
-  int bx, by;   // the general branch: equal segments only (smrf_ring_plan's residency classes count on `by` growing with the dispatch id)
-  smrf_xcd_tile(!SMRF_RING_XCD_REMAP || a.plain_tiles, [&] { return a.seg_cls == 0; }, bx, by);
-#ifdef SMRF_RING_DBG_CLOCK   // timing experiment only: the shader clock this workgroup ran at, left in the output's first two cells
-  const unsigned long long dbg_t0 = __builtin_amdgcn_s_memtime(), dbg_q0 = __builtin_amdgcn_s_memrealtime();
-#endif
-#ifdef SMRF_RING_DBG_TS
-  const unsigned long long dbg_ts0 = __builtin_amdgcn_s_memrealtime();
-#endif
-  const int x0 = bx * TW;
-  const int x = x0 + tid;
-  int ys, ye;                                            // global output rows [ys, ye)
-  if (a.seg_cls > 0) {                                   // segments of unequal length (smrf_ring_plan: residency classes)
-    int cls = 0;
-    for (int c = 1; c < a.seg_cls; ++c) cls += by >= a.seg_first[c] ? 1 : 0;
-    ys = a.out_row0 + a.seg_row0[cls] + (by - a.seg_first[cls]) * a.seg_len[cls];
-    ye = min(a.out_row0 + a.out_rows, ys + a.seg_len[cls]);
-    if (ys >= ye) return;                                // (lengths are rounded up: a trailing segment may be empty)
-  } else {
-    ys = a.out_row0 + by * a.seg;
-    ye = min(a.out_row0 + a.out_rows, ys + a.seg);
-  }
-  constexpr int NPOS = C::NPOS, W = C::W;
-  // lane-owned staged cells: positions tid + i*TW of the TW+2R wide row; only the last can be absent
-  const bool has_last = tid + (NPOS - 1) * TW < W;
-  int cpos[NPOS];
-#pragma unroll
-  for (int i = 0; i < NPOS; ++i) cpos[i] = smrf_fold(x0 - R + tid + (tid + i * TW < W ? i * TW : 0), a.cols);
-  const int last_in = a.in_rows - 1;
-  // halo cells shared out over the waves (HaloCfg): this lane's halo cell and the column it is loaded from
-  using H = HaloCfg<T, R, TW, NP>;
-  constexpr bool BAL = H::OK;
-  HaloLane hl;
-  hl.wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  {
-    const int h = (hl.wave % H::NH) * 64 + (tid & 63);
-    hl.act = BAL && h < H::HW;
-    hl.pos = hl.act ? TW + h : TW;
-  }
-  const int hcol = smrf_fold(x0 - R + hl.pos, a.cols);
-  static_assert(TW == kRingTW, "the table is shared by the workgroup's four waves: workgroup barriers between the phases");
-  auto phase_sync = [&]() { __syncthreads(); };
-  const bool flag = a.mask != nullptr;
-  const int xc = x < a.cols ? x : a.cols - 1;
-
-  // ring: between pairs, slot s holds the partial result of output row (next input row) - R + s
-  T acc[2 * R];
-#pragma unroll
-  for (int i = 0; i < 2 * R; ++i) acc[i] = ident<T>(DIL);
-
-  T2 pf[NP][NPOS];                                       // next batch, this lane's staged cells
-  T2 pfh[H::NJ];                                         // BAL: next batch, this lane's halo cell of its wave's jobs
-  T outv[ROWS], lastv[ROWS];
-#pragma unroll
-  for (int i = 0; i < ROWS; ++i) { outv[i] = T(0); lastv[i] = T(0); }
-
-  // The row loop starts DELTA rows early so that the ROWS outputs a batch completes are either all
-  // at or above ys or all below it (rows before ys - R only feed outputs that are never written).
-  constexpr int DELTA = (ROWS - (2 * R) % ROWS) % ROWS;
-  const int ystart = ys - R - DELTA;
-  RowFold rf(ystart, a.img_rows);                        // tracks the NEXT batch to prefetch
-  // buffer addressing of the common cases (SMRF_RING_BUF): descriptors based at the first row of each plane this
-  // workgroup touches there, byte offsets of the lane's columns; the host keeps a segment's span below 2 GiB (ring_launch_np)
-  constexpr bool BUF = ring_buf_on<T, R, TW, NP>();
-  constexpr bool RARE = C::INPLACE && SMRF_RING_RARE_OPAQUE(T, R);
-  const int bi = max(0, ystart - a.in_row0);                       // first band row of `in` a fast-path batch can start at
-  const int bl = max(0, ys - 2 * R - DELTA - a.out_row0);          // ... of `last` (first batch: outputs of rows ystart - R ...)
-  const int bo = ys - a.out_row0;                                  // ... of `out`, `mask`, `when`
-  const unsigned rowb = (unsigned)a.ld * (unsigned)sizeof(T);     // bytes per row
-  // (descriptors of planes a launch does not have are built from null pointers and never used)
-  const smrf_rsrc_t rs_in = smrf_make_rsrc(a.in + (long long)bi * a.ld);
-  const smrf_rsrc_t rs_out = smrf_make_rsrc(a.out + (long long)bo * a.ld);
-  const smrf_rsrc_t rs_last = smrf_make_rsrc(flag ? a.last + (long long)bl * a.ld : nullptr);
-  const smrf_rsrc_t rs_mask = smrf_make_rsrc(flag ? a.mask + (long long)bo * a.ld : nullptr);
-  const smrf_rsrc_t rs_when = smrf_make_rsrc(flag && a.when != nullptr ? a.when + (long long)bo * a.ld : nullptr);
-  unsigned cposb[NPOS], hcolb = 0, xb = 0, xcb = 0;
-  if constexpr (BUF) {
-#pragma unroll
-    for (int i = 0; i < NPOS; ++i) cposb[i] = (unsigned)cpos[i] * (unsigned)sizeof(T);
-    hcolb = (unsigned)hcol * (unsigned)sizeof(T);
-    xb = (unsigned)x * (unsigned)sizeof(T);
-    xcb = (unsigned)xc * (unsigned)sizeof(T);
-  }
-  auto prefetch = [&]() {
-    const int l0 = rf.p - a.in_row0;
-    if (rf.p + ROWS <= rf.n && l0 >= 0 && l0 + ROWS - 1 <= last_in) {
-      // common case: ROWS consecutive rows inside the band, no reflection: one address, row strides
-      SMRF_MARK("prefetch");
-      if constexpr (BUF) {
-        const unsigned s0 = (unsigned)(l0 - bi) * rowb;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-#pragma unroll
-          for (int i = 0; i < (BAL ? 1 : NPOS); ++i) {
-            pf[p][i].x = smrf_buf_load(rs_in, cposb[i], s0 + (unsigned)(2 * p) * rowb, T());
-            pf[p][i].y = smrf_buf_load(rs_in, cposb[i], s0 + (unsigned)(2 * p + 1) * rowb, T());
-          }
-        }
-        if constexpr (BAL) {
-#pragma unroll
-          for (int j = 0; j < H::NJ; ++j) {
-            const int q = hl.wave + H::WAVES * j;
-            const int pq = q < H::NQ ? q / H::NH : 0;
-            pfh[j].x = smrf_buf_load(rs_in, hcolb, s0 + (unsigned)(2 * pq) * rowb, T());
-            pfh[j].y = smrf_buf_load(rs_in, hcolb, s0 + (unsigned)(2 * pq + 1) * rowb, T());
-          }
-        }
-      } else {
-      const T* r0 = a.in + (long long)l0 * a.ld;
-#pragma unroll
-      for (int p = 0; p < NP; ++p) {
-#pragma unroll
-        for (int i = 0; i < (BAL ? 1 : NPOS); ++i) {
-          pf[p][i].x = r0[(long long)(2 * p) * a.ld + cpos[i]];
-          pf[p][i].y = r0[(long long)(2 * p + 1) * a.ld + cpos[i]];
-        }
-      }
-      if constexpr (BAL) {
-#pragma unroll
-        for (int j = 0; j < H::NJ; ++j) {
-          const int q = hl.wave + H::WAVES * j;            // wave-job: row pair q / NH (inactive lanes load a valid cell)
-          const int pq = q < H::NQ ? q / H::NH : 0;
-          pfh[j].x = r0[(long long)(2 * pq) * a.ld + hcol];
-          pfh[j].y = r0[(long long)(2 * pq + 1) * a.ld + hcol];
-        }
-      }
-      }
-    } else {
-      SMRF_MARK("rare");
-#pragma unroll
-      for (int p = 0; p < NP; ++p) {
-        int la = rf.at(2 * p) - a.in_row0;
-        int lb = rf.at(2 * p + 1) - a.in_row0;
-        la = la < 0 ? 0 : (la > last_in ? last_in : la);   // only rows outside the segment's halo clamp
-        lb = lb < 0 ? 0 : (lb > last_in ? last_in : lb);
-        const T* ra = a.in + (long long)la * a.ld;
-        const T* rb = a.in + (long long)lb * a.ld;
-#pragma unroll
-        for (int i = 0; i < (BAL ? 1 : NPOS); ++i) { const int c = smrf_rare<RARE>(cpos[i]); pf[p][i].x = ra[c]; pf[p][i].y = rb[c]; }
-      }
-      if constexpr (BAL) {
-#pragma unroll
-        for (int j = 0; j < H::NJ; ++j) {
-          const int q = hl.wave + H::WAVES * j;
-          const int pq = q < H::NQ ? q / H::NH : 0;
-          int la = rf.at(2 * pq) - a.in_row0;
-          int lb = rf.at(2 * pq + 1) - a.in_row0;
-          la = la < 0 ? 0 : (la > last_in ? last_in : la);
-          lb = lb < 0 ? 0 : (lb > last_in ? last_in : lb);
-          const int hc = smrf_rare<RARE>(hcol);
-          pfh[j].x = a.in[(long long)la * a.ld + hc];
-          pfh[j].y = a.in[(long long)lb * a.ld + hc];
-        }
-      }
-    }
-    SMRF_MARK("prefetch");
-    rf.advance(ROWS);
-  };
-  // one completed output cell, general form: NaN rule, store, flag step (sparse or dense)
-  auto emit = [&](int yo, long long off, T val, T lastval) {
-    if (a.nan_aware) {
-      // scipy: the first visited footprint element (offset (-R, 0)) decides NaN-ness
-      const int ly = smrf_fold(yo - R, a.img_rows) - a.in_row0;
-      const T first = a.in[(long long)ly * a.ld + smrf_rare<RARE>(x)];
-      if (first != first) val = qnan<T>();
-    }
-    smrf_store_out(&a.out[off], val, a.nt);
-    if (flag) smrf_flag_cell(a, off, lastval, val);
-  };
-  // the common case of a batch (all ROWS rows inside the segment, no NaN rule, sparse flags) as straight-line code per
-  // (store kind, flag step): the uniform tests are made once per batch, not once per cell - scalar branches between
-  // the VALU instructions of a kernel that runs at 2-3 waves per SIMD are not free (profiles/r02_issue_rate_ubench.md)
-  auto emit_rows = [&]<bool NT, bool FLAG>(std::bool_constant<NT>, std::bool_constant<FLAG>, long long off0, int ro0) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < ROWS; ++i) {
-      const long long off = off0 + (long long)i * a.ld;
-      const unsigned so = (unsigned)(ro0 - bo + i) * rowb;   // BUF: row offset from the segment's first output row
-      if constexpr (BUF) smrf_buf_store<NT>(rs_out, xb, so, outv[i]);
-      else if constexpr (NT) __builtin_nontemporal_store(outv[i], &a.out[off]);
-      else a.out[off] = outv[i];
-      if constexpr (FLAG) {
-        const T diff = lastv[i] - outv[i];                   // raster dtype
-        bool hit;                                            // float64 comparison (NumPy 2); fp32: smrf_float_below
-        if constexpr (sizeof(T) == 4) hit = diff > a.thr_lo;
-        else hit = (double)diff > a.thr;
-        if (hit) {
-          if constexpr (BUF) {
-            const unsigned sm = (unsigned)(ro0 - bo + i) * (unsigned)a.ld;
-            smrf_buf_store_u8(rs_mask, (unsigned)x, sm, (uint8_t)1);
-            if (a.when != nullptr) smrf_buf_store_u8(rs_when, (unsigned)x, sm, (uint8_t)a.widx);
-          } else {
-            a.mask[off] = 1;
-            if (a.when != nullptr) a.when[off] = (uint8_t)a.widx;
-          }
-        }
-      }
-    }
-  };
-  // outputs of the batch whose first input row was yyb; written one iteration late so that no
-  // store is younger than the prefetch loads the loop waits for
-  auto epilogue = [&](int yyb) {
-    const int yob = yyb - R;                               // first output row of the batch
-    if (yob < ys || x >= a.cols) return;                   // (aligned: yob < ys means all rows are)
-    const long long off0 = (long long)(yob - a.out_row0) * a.ld + x;
-    if (yob + ROWS <= ye && !a.nan_aware && !a.dense) {
-      const int ro0 = yob - a.out_row0;
-      if (flag) {
-        if (a.nt) { SMRF_MARK("epilogue:nt1:flag1"); emit_rows(std::true_type{}, std::true_type{}, off0, ro0); }
-        else { SMRF_MARK("epilogue:nt0:flag1"); emit_rows(std::false_type{}, std::true_type{}, off0, ro0); }
-      } else {
-        if (a.nt) { SMRF_MARK("epilogue:nt1:flag0"); emit_rows(std::true_type{}, std::false_type{}, off0, ro0); }
-        else { SMRF_MARK("epilogue:nt0:flag0"); emit_rows(std::false_type{}, std::false_type{}, off0, ro0); }
-      }
-      SMRF_MARK("epilogue");
-    } else {
-      SMRF_MARK("rare");
-      const long long off0r = (long long)(yob - a.out_row0) * a.ld + smrf_rare<RARE>(x);
-#pragma unroll
-      for (int i = 0; i < ROWS; ++i)
-        if (yob + i < ye) emit(yob + i, off0r + (long long)i * a.ld, outv[i], lastv[i]);
-      SMRF_MARK("epilogue");
-    }
-  };
-  auto load_last = [&](int yyb) {
-    if (!flag) return;
-    const int y0 = yyb - R - a.out_row0;
-    if (y0 >= 0 && y0 + ROWS <= a.out_rows) {
-      SMRF_MARK("last");
-      if constexpr (BUF) {
-        const unsigned s0 = (unsigned)(y0 - bl) * rowb;
-#pragma unroll
-        for (int i = 0; i < ROWS; ++i) lastv[i] = smrf_buf_load(rs_last, xcb, s0 + (unsigned)i * rowb, T());
-      } else {
-      const T* l0 = a.last + (long long)y0 * a.ld + xc;
-#pragma unroll
-      for (int i = 0; i < ROWS; ++i) lastv[i] = l0[(long long)i * a.ld];
-      }
-    } else {
-      SMRF_MARK("rare");
-#pragma unroll
-      for (int i = 0; i < ROWS; ++i) {
-        int yo = y0 + i;
-        yo = yo < 0 ? 0 : (yo >= a.out_rows ? a.out_rows - 1 : yo);
-        lastv[i] = a.last[(long long)yo * a.ld + smrf_rare<RARE>(xc)];
-      }
-    }
-    SMRF_MARK("last");
-  };
-
-  prefetch();
-  int par = 0;                                           // which level-0 copy this batch uses
-  for (int yy0 = ystart; yy0 < ye + R; yy0 += ROWS, par ^= 1) {
-    // (1) stage the prefetched rows into this batch's level-0 copy.  The other copy may still be
-    //     read by a slower wave (its own cells of the previous batch); the higher levels are only
-    //     written after the barrier below, which every wave reaches after its previous consume.
-    SMRF_MARK("stage");
-    T2 v[NP][NPOS];
-    T2 vh[H::NJ];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-#pragma unroll
-      for (int i = 0; i < (BAL ? 1 : NPOS); ++i) {
-        v[p][i] = pf[p][i];
-        if (i < NPOS - 1 || has_last)
-          lds_write2((unsigned)(size_t)(__attribute__((address_space(3))) void*)(L + (p * NLEV + par) * WP + tid + i * TW), v[p][i]);
-      }
-    }
-    if constexpr (BAL) {
-#pragma unroll
-      for (int j = 0; j < H::NJ; ++j) {
-        vh[j] = pfh[j];
-        const int q = hl.wave + H::WAVES * j;
-        if (hl.act && q < H::NQ)
-          lds_write2((unsigned)(size_t)(__attribute__((address_space(3))) void*)(L + ((q / H::NH) * NLEV + par) * WP + hl.pos), vh[j]);
-      }
-    }
-    lds_wait<0>();                                         // the compiler does not count asm stores: complete them before the barrier
-    phase_sync();
-    SMRF_MARK("epilogue");
-    if (yy0 > ystart) epilogue(yy0 - ROWS);
-    SMRF_MARK("prefetch");
-    if (yy0 + ROWS < ye + R) prefetch();
-    SMRF_MARK("last");
-    load_last(yy0);
-    SMRF_MARK("build");
-
-    if constexpr (BAL) {
-      // ring_build_consume with the halo cells as wave-jobs: every wave builds its own 256 cells' worth of each row
-      // pair plus its share of the halo, so the waves reach the phase barriers together
-      __builtin_amdgcn_s_setprio(kRingBuildPrio);
-      ring_base<T, R, DIL, TW, NP, 1, 0>(L, par, tid, true, v);
-      SMRF_MARK("build:halo");
-      ring_base_halo<T, R, DIL, TW, NP>(L, par, hl, vh);
-      SMRF_MARK("build");
-      phase_sync();
-      if constexpr (C::J > C::JB) {
-        ring_upper<T, R, DIL, TW, NP, 1, 0>(L, tid, true, v);
-        ring_upper_halo<T, R, DIL, TW, NP>(L, hl, vh);
-        phase_sync();
-      }
-      __builtin_amdgcn_s_setprio(0);
-      ring_consume<T, R, DIL, TW, NP>(L, par, tid, acc, outv);
-    } else {
-      ring_build_consume<T, R, DIL, TW, NP, NPOS, 0>(L, par, tid, has_last, v, acc, outv, phase_sync);
-    }
-  }
-  SMRF_MARK("tail");
-  {
-    const int nb = (ye + R - ystart + ROWS - 1) / ROWS;
-    epilogue(ystart + (nb - 1) * ROWS);
-  }
-#ifdef SMRF_RING_DBG_TS   // timing experiment only (tools/experiments/ring_tails.py): when and where this workgroup ran, left in
-  if (tid == 0 && x0 + 6 <= a.cols) {   // the first cells of its segment's first row (the RESULT IS WRONG there)
-    __threadfence();
-    unsigned xcc, hwid;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    T* const o = a.out + (long long)(ys - a.out_row0) * a.ld + x0;
-    o[0] = (T)(float)(dbg_ts0 & 0x7fffff);
-    o[1] = (T)(float)(__builtin_amdgcn_s_memrealtime() & 0x7fffff);
-    o[2] = (T)(float)(xcc & 0xf);
-    o[3] = (T)(float)(hwid & 0xffff);
-    o[4] = (T)(float)(blockIdx.y * gridDim.x + blockIdx.x);
-    o[5] = (T)(float)(ye - ys);
-  }
-#endif
-#ifdef SMRF_RING_DBG_CLOCK
-  if (bx == gridDim.x / 2 && by == gridDim.y / 2 && tid == 0) {
-    __threadfence();
-    a.out[0] = (T)(float)(__builtin_amdgcn_s_memtime() - dbg_t0);
-    a.out[1] = (T)(float)(__builtin_amdgcn_s_memrealtime() - dbg_q0);
-  }
-#endif
+  constexpr bool CROSS = false;
+#include "ring_kernel_body.inc"
 }
 
-template <typename T, int R, bool DIL, int NP>
+template <int R, int TW, int NP>
+__global__ __launch_bounds__(TW, (ring_cross_occ<R, TW, NP>()))
+void ring_cross_kernel(const DiskArgs<float> a) {
+  using T = float;
+  constexpr bool DIL = true, CROSS = true;
+#include "ring_kernel_body.inc"
+}
+
+template <typename T, int R, bool DIL, int NP, bool CROSS = false>
 int ring_launch_np(const DiskArgs<T>& a_in, hipStream_t stream, bool probe_only, int* seg_if_launched) {
   constexpr int TW = kRingTW;
   using C = RingCfg<T, R, TW, NP>;
-  constexpr auto kern = ring_kernel<T, R, DIL, TW, NP>;
+  constexpr auto kern = [] {
+    if constexpr (CROSS) return ring_cross_kernel<R, TW, NP>;
+    else return ring_kernel<T, R, DIL, TW, NP>;
+  }();
+  constexpr int occ = [] {
+    if constexpr (CROSS) return ring_cross_occ<R, TW, NP>();
+    else return (int)C::OCC;
+  }();
   int resident;
   bool first;
   if (int rc = smrf_resident<kern>(TW, C::LDS_BYTES, resident, first)) return rc;
   if (first && smrf_sw().ring_debug)
     fprintf(stderr, "smrf ring: R=%d %s%s NP=%d G=%d%s LDS=%zu built for %d waves/SIMD, %d workgroups/CU resident\n", R,
-            sizeof(T) == 4 ? "f32" : "f64", DIL ? " dilate" : " erode", NP, C::G, C::INPLACE ? " in-place" : "", C::LDS_BYTES,
-            C::OCC, resident);
+            sizeof(T) == 4 ? "f32" : "f64", CROSS ? " dilate of the cross" : DIL ? " dilate" : " erode", NP, C::G, C::INPLACE ? " in-place" : "", C::LDS_BYTES,
+            occ, resident);
   DiskArgs<T> a = a_in;
   const int strips = (a.cols + TW - 1) / TW;
   // the built-in slope of the unequal segments is for fp32 rasters whose strip count divides 256 (smrf_ring_plan says why);
@@ -1608,6 +1309,15 @@ int ring_launch(const DiskArgs<T>& a_in, hipStream_t stream) {
     if (mode == 1 || (mode < 0 && seg >= 8 * R)) return ring_launch_np<T, R, DIL, NPI>(a_in, stream, false, nullptr);
   }
   return ring_launch_np<T, R, DIL, NP>(a_in, stream, false, nullptr);
+}
+
+// the cross on load exists in one form per radius: SMRF_CROSS_NP row pairs per batch, or the plain dilation's - where a radius is
+// dual the in-place instance's (its fewer row pairs per batch leave the registers for the cross's cells)
+template <int R>
+int ring_cross_launch(const DiskArgs<float>& a_in, hipStream_t stream) {
+  constexpr int NP = SMRF_CROSS_NP(R) > 0 ? SMRF_CROSS_NP(R)
+                     : ring_tuned_inplace_dual<float>(R) && SMRF_RING_INPLACE(float, R) ? SMRF_RING_INPLACE_NP(float, R) : SMRF_RING_NP(float, R);
+  return ring_launch_np<float, R, true, NP, true>(a_in, stream, false, nullptr);
 }
 
 }  // namespace smrf

@@ -1,7 +1,8 @@
 // Which launch every window of progressive_filter takes: the whole rule, as tables and one pure function (smrf_pf_route).
 // The whole-raster driver (morph.hip, progressive_filter_api) executes the plan this function makes, and the row-band driver
 // (neilpy_amd/sharded.py) asks the same function through smrf_pf_plan of the C ABI.  Plain C++, no HIP: included by
-// smrf_common.h and compiled on its own by tests/test_pf_route_host.py.
+// smrf_common.h and compiled on its own by tests/test_pf_route_host.py.  smrf_pf_fold, a second pure function after it, marks the
+// two-pass windows whose erosion is taken inside their dilation pass (tests/test_pf_fold_host.py).
 #pragma once
 #include <cstdint>
 
@@ -116,6 +117,21 @@ inline bool smrf_inc_erode_adopted(int elem_size, int radius) {
 }
 
 // ------------------------------------------------------------------------------------------
+// cross on load (morph_ring.h, ring_cross_kernel; ring_part.hip instantiates one per radius)
+// ------------------------------------------------------------------------------------------
+// The radii whose leftover set P_R is empty (ero_inc.inc; morph_incero.h checks this list against it): there
+// e_R = erode(e_{R-1}, 5-point cross) exactly, and the window's dilation pass can take that cross while it loads e_{R-1}.
+constexpr bool smrf_dil_cross_has(int elem_size, int radius) {
+  return elem_size == 4 && (radius == 16 || radius == 21 || radius == 36);
+}
+namespace smrf {
+#include "dil_cross_adopt.inc"
+}  // namespace smrf
+inline bool smrf_dil_cross_adopted(int elem_size, int radius) {
+  return smrf_dil_cross_has(elem_size, radius) && smrf::kDilCrossAdoptF32[radius] != 0;
+}
+
+// ------------------------------------------------------------------------------------------
 // the plan
 // ------------------------------------------------------------------------------------------
 struct SmrfPfRules {
@@ -129,6 +145,7 @@ struct SmrfPfRules {
                    // longest band with its two-sided margin), fused openings up to kFusedSmallRadius only, and no incremental erosion
                    // (its kernel takes whole rasters: a band's e_{R-1} margin rows are stale after a halo exchange);
                    // 2 = a row band whose launches cannot be chained either (the edge-first split of overlap=True, a single band)
+  int dil_cross;   // SMRF_DIL_CROSS (smrf_pf_fold only): 0 = never, 1 = where dil_cross_adopt.inc says it wins, 2 = every eligible window
 };
 
 // Window by window, for i = 0 .. n - 1 (windows[i] >= 0):
@@ -172,3 +189,33 @@ inline void smrf_pf_route(const SmrfPfRules& k, const int32_t* windows, int n, i
     ++i;
   }
 }
+
+// Which two-pass windows fold their erosion into their dilation pass (cross on load), after smrf_pf_route has made route[] and
+// ero_inc[] (both are read only and keep their meaning: smrf_pf_ero_inc_windows and smrf_pf_plan report them as before).
+//   fold[i] = kPfFoldCross  window i launches no erosion: its dilation reads e_{R-1} (the plane of window i - 1's erosion), takes the
+//                           5-point cross on load and writes the opened surface into the spare plane.  When: fp32, a whole raster
+//                           without NaN, impl auto or ring, windows i - 1 and i both two ring passes, radius = the previous radius
+//                           + 1, P_radius empty (smrf_dil_cross_has), window i - 1 not folded itself (its e is then not in the
+//                           workspace), and SMRF_DIL_CROSS = 2 - or = 1, dil_cross_adopt.inc adopts the radius and a window
+//                           follows: under the table the call's last window keeps its erosion pass, so that the workspace ends with
+//                           the last window's eroded and opened surfaces as it always has (the tests of the incremental erosion
+//                           read them there).
+//   fold[i] = kPfFoldAfter  window i - 1 was folded: the workspace holds e_{R-2}, not e_{R-1}, so window i runs the ring erosion
+//                           whatever ero_inc[i] says (smrf_pf_runs_inc), also under SMRF_ERO_INC = 2
+//   fold[i] = kPfFoldNone   everything else
+constexpr uint8_t kPfFoldNone = 0, kPfFoldCross = 1, kPfFoldAfter = 2;
+inline void smrf_pf_fold(const SmrfPfRules& k, const int32_t* windows, const int32_t* route, const uint8_t* ero_inc, int n,
+                         uint8_t* fold) {
+  (void)ero_inc;   // (a window the incremental erosion would take is folded all the same: the fold removes the pass, not a part of it)
+  const bool ok = k.dil_cross != 0 && !k.band && !k.nan_aware && k.elem_size == 4 && (k.impl == kPfImplAuto || k.impl == kPfImplRing);
+  for (int i = 0; i < n; ++i) {
+    fold[i] = i > 0 && fold[i - 1] == kPfFoldCross ? kPfFoldAfter : kPfFoldNone;
+    if (!ok || i == 0 || fold[i] != kPfFoldNone) continue;
+    const int r = windows[i];
+    if (route[i] != kPfRouteTwoPass || route[i - 1] != kPfRouteTwoPass || r != windows[i - 1] + 1 || !smrf_dil_cross_has(k.elem_size, r))
+      continue;
+    if (k.dil_cross == 2 || (smrf_dil_cross_adopted(k.elem_size, r) && i + 1 < n)) fold[i] = kPfFoldCross;
+  }
+}
+// window i's erosion comes from inc_erode_kernel: the route's flag, unless the window is folded or follows a folded one
+inline bool smrf_pf_runs_inc(const uint8_t* ero_inc, const uint8_t* fold, int i) { return ero_inc[i] != 0 && fold[i] == kPfFoldNone; }

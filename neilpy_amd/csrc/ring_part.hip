@@ -23,6 +23,10 @@ int launch_r(const DiskArgs<elem_t>& a, int mode, hipStream_t s) {
     if constexpr (smrf_fused_radius((int)sizeof(elem_t), R)) return smrf::fused_launch<elem_t, R>(a, s);
     else return smrf_fail(SMRF_E_UNSUPPORTED, "no fused opening kernel for radius %d at this dtype", R);
   }
+  if (mode == SMRF_RING_DILATE_CROSS) {
+    if constexpr (smrf_dil_cross_has((int)sizeof(elem_t), R)) return smrf::ring_cross_launch<R>(a, s);
+    else return smrf_fail(SMRF_E_UNSUPPORTED, "no cross-on-load dilation for radius %d at this dtype", R);
+  }
   return mode == SMRF_RING_DILATE ? smrf::ring_launch<elem_t, R, true>(a, s) : smrf::ring_launch<elem_t, R, false>(a, s);
 }
 }  // namespace

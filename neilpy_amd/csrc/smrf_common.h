@@ -78,6 +78,8 @@ struct SmrfSwitches {
   int ring_debug;     // SMRF_RING_DEBUG: print each instance's geometry once
   int ero_inc;        // SMRF_ERO_INC: window R's erosion from window R-1's (morph_incero.h): 0 never, 1 where ero_inc_adopt.inc says
                       // it wins (default), 2 every eligible window
+  int dil_cross;      // SMRF_DIL_CROSS: a rim-free window's erosion taken inside its dilation pass (morph_ring.h, cross on load): 0 never,
+                      // 1 where dil_cross_adopt.inc says it wins (default), 2 every eligible window
 };
 SMRF_HIDDEN const SmrfSwitches& smrf_sw();
 
@@ -159,7 +161,9 @@ struct DiskArgs {
 
 // ring-kernel dispatchers, one per (dtype, radius % SMRF_RING_PARTS); defined in ring_part.hip.
 // mode: erosion, dilation (+ flag step when mask != NULL), or the fused opening + flag of morph_fused.h (in = last)
-enum { SMRF_RING_ERODE = 0, SMRF_RING_DILATE = 1, SMRF_RING_FUSED_OPEN = 2 };
+// SMRF_RING_DILATE_CROSS: the dilation + flag step whose `in` is e_{R-1} and whose loads take the 5-point cross (fp32, the radii of
+// smrf_dil_cross_has, whole rasters without NaN)
+enum { SMRF_RING_ERODE = 0, SMRF_RING_DILATE = 1, SMRF_RING_FUSED_OPEN = 2, SMRF_RING_DILATE_CROSS = 3 };
 // incremental erosion of progressive_filter's consecutive windows (morph_incero.h, defined in incero.hip); which radii have an
 // instance and which the default routing adopts: pf_route.h
 SMRF_HIDDEN int smrf_inc_erode_f32(const float* e_prev, const float* last, float* out, int rows, int cols, long long ld,
