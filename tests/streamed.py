@@ -1,6 +1,9 @@
 """The side-stream harness (a plain helper module, no test in it; its proof is in tests/test_streamed_host.py and at the
 head of tests/test_gpu_streams.py).
 
+The cases it is run on are those tests/family_cases.py marks ``stream=True``; result trees are read with that module's
+``rebuild`` and ``to_numpy``.
+
 ``run_streamed(fn, inputs, kw, name=, reference=, ctx=)`` calls a public function with a fresh non-default
 ``torch.cuda.Stream()`` as the current stream and combines three checks:
 
@@ -33,6 +36,7 @@ import re
 
 import numpy as np
 
+from family_cases import rebuild, to_numpy
 from guarded import guarded
 
 DEVICE = "cuda:0"
@@ -198,7 +202,6 @@ def run_streamed(fn, inputs, kw=None, *, name, reference=None, ctx=None, stream=
     ``lib`` / ``slots``: another object behind the proxy (the stand-ins' fake library).  ``stats``: a dict that gets
     ``allocations`` added.  Returns the result as NumPy arrays."""
     import torch
-    from test_gpu_guarded import _np, _rebuild
     side = stream if stream is not None else side_stream()
     assert side.cuda_stream != 0 and side != torch.cuda.default_stream()
     sleep = delay(delay_ms)
@@ -224,7 +227,7 @@ def run_streamed(fn, inputs, kw=None, *, name, reference=None, ctx=None, stream=
                         t.copy_(r, non_blocking=True)
                 res = fn(*args, **(kw or {}))
                 g.before_fill = None
-                got = _rebuild(res, _np)                 # .cpu() on the side stream: waits for it, and for nothing else
+                got = rebuild(res, to_numpy)             # .cpu() on the side stream: waits for it, and for nothing else
                 g.check()
         finally:
             g.before_fill = None

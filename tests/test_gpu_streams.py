@@ -5,12 +5,12 @@ First the harness proves itself with stand-ins, torch ops on the harness's own m
 computes under the default stream reads the decoy; one whose last copy runs on the default stream ends up as poison; one
 whose library call carries stream 0 fails the handle check - each in 10 of 10 repetitions at the delay D and at D / 4.
 
-Then one ``run_streamed`` case per name of tests/test_gpu_guarded.py's GUARDED (and per dtype where the function takes
-both), built from what that module builds for the name: the same rasters, keywords, window lists and reference
-comparisons, at a single shape each - (67, 131) with 2 % NaN for the rasters, (70, 300) with one window list per route of
-``smrf_pf_plan`` for progressive_filter - plus the spline pair, the one-GPU band driver, two NumPy-in NumPy-out calls of
-slope (the second through the pinned staging buffers) and two streams in one thread that share an input and the library's
-cached device tables.  Shapes are the guarded module's job; this one varies the stream only.
+Then, per name of tests/family_cases.py's GUARDED, the cases that name's builder marks ``stream=True``: cases of the
+guarded module's own sweep, the very dicts ``run_guarded`` gets, at a single shape each (and per dtype where the function
+takes both) - (67, 131) with 2 % NaN for the rasters, (70, 300) with one window list per route of ``smrf_pf_plan`` for
+progressive_filter - plus the table's two extras (the spline pair and the one-GPU band driver), two NumPy-in NumPy-out calls
+of slope (the second through the pinned staging buffers) and two streams in one thread that share an input and the
+library's cached device tables.  No case is built here; shapes are the guarded module's job, this one varies the stream only.
 
 Measured on an MI355X (the module prints these figures; D is a sensitivity setting, no tolerance - correct code passes at
 any D):
@@ -33,27 +33,15 @@ library of its own: chamfer_distance failed on data (0.474 for 0.858), nearest_p
 import numpy as np
 import pytest
 
-import focal_numpy as fnp
-import morph_numpy as mn
-import morphometry_numpy as mnp
-import nearest_numpy as nn
-import points_numpy as pn
-import relief_numpy as rn
-import surface_numpy as sn
-import terrain_numpy as tn
-import voxel_numpy as vn
+import family_cases as FC
 import streamed as S
-import test_gpu_guarded as T
-from conftest import golden, load_sample
-from family_checks import assert_exact
+import surface_numpy as sn
+from family_cases import F, F32, F64, GUARDED, NAN_SHAPE as SHAPE
 from streamed import EXPECTED, Host, run_streamed, standin_verdict
-from test_gpu_guarded import F, F32, F64, GUARDED
 
 pytestmark = pytest.mark.gpu
 
 STATS = {}                       # allocations served over the module's run (printed by the last test)
-SHAPE = T.NAN_SHAPE
-PF_SHAPE = T.PF_SHAPES[0]
 
 
 def streamed(fn, inputs, **k):
@@ -94,270 +82,31 @@ def test_standins(gpu_device, kind, share):
 
 
 # ------------------------------------------------------------------------------------------
-# one case per guarded name
+# the stream-marked cases of tests/family_cases.py's table
 # ------------------------------------------------------------------------------------------
-CASES = {}                       # name -> generator of run_streamed keyword dicts
+# the band driver posts its exchanges on a stream of its own making: those handles are its own business, the
+# wait_event / wait_stream wiring to the caller's stream is what the data check sees
+OPTIONS = {"sharded": dict(own_streams=True)}
 
 
-def cases(*names):
-    def register(f):
-        for n in names:
-            assert n in GUARDED and n not in CASES, n
-            CASES[n] = (lambda n=n: f(n))
-        return f
-    return register
-
-
-def nan_raster(dtype):
-    """cases_of()'s last raster: (67, 131) with 2 % NaN cells"""
-    return T.raster(SHAPE, dtype, nan=True, seed=7), (SHAPE, np.dtype(dtype).name, "nan")
-
-
-def both(f):
-    """f(name, dtype, Z, ctx) -> case dicts, for float32 and float64"""
-    def g(name):
-        for dtype in (F32, F64):
-            Z, ctx = nan_raster(dtype)
-            yield from f(name, dtype, Z, ctx)
-    return g
-
-
-@cases(*T.SURFACE)
-@both
-def surface(fn, dtype, Z, ctx):
-    from test_gpu_surface import compare
-    kw = T.golden_kw("surface.npz", fn)
-    yield dict(fn=lambda Zt: F(fn)(Zt, **sn.decode_kw(kw)), inputs=[Z], ctx=(ctx, kw),
-               reference=lambda got: compare(fn, Z, kw, got, sn.run(fn, Z, kw)))
-
-
-@cases("focal_convolve", "std", "reduce_peaks", "topographic_position_index")
-@both
-def focal(fn, dtype, Z, ctx):
-    from test_gpu_focal import assert_bits, check_tpi
-    w = T.focal_kernels()["7x7 with zero taps"]
-    pos = np.abs(w) + (w != 0) * 0.1
-    if fn == "focal_convolve":
-        want = fnp.convolve(Z, w)
-        yield dict(fn=lambda Zt: F("focal_convolve")(Zt, w), inputs=[Z], ctx=ctx, reference=lambda got: assert_bits(got, want, ctx))
-    elif fn == "std":
-        want = fnp.std(Z, pos)
-        yield dict(fn=lambda Zt: F("std")(Zt, pos), inputs=[Z], ctx=ctx, reference=lambda got: assert_bits(got, want, ctx))
-    elif fn == "reduce_peaks":
-        want = fnp.reduce_peaks(Z, 3)
-        yield dict(fn=lambda Zt: F("reduce_peaks")(Zt, 3), inputs=[Z], ctx=ctx, reference=lambda got: assert_bits(got, want, ctx))
-    else:
-        kw = dict(radius=4, standardize=True)                # the partials workspace and the single-workgroup reduce
-        yield dict(fn=lambda Zt: F("topographic_position_index")(Zt, **kw), inputs=[Z], ctx=(ctx, kw),
-                   reference=lambda got: check_tpi(Z, got, kw, ctx))
-
-
-@cases(*T.TERRAIN)
-@both
-def terrain(fn, dtype, Z, ctx):
-    from neilpy_amd import _lib
-    from test_gpu_terrain import compare
-    kw = dict(T.golden_kw("terrain.npz", fn), lookup_pixels=_lib.TERRAIN_HALO_CAP["f32" if dtype == F32 else "f64"] + 1)
-    if fn == "geomorphons":
-        kw["enhance"] = True
-    kw.pop("neighbors", None)
-    want = tn.run(fn, Z, kw)
-    yield dict(fn=lambda Zt: T.terrain_call(fn, Zt, kw, T.AUTO), inputs=[Z], ctx=(ctx, kw),
-               reference=lambda got: compare(fn, Z, kw, got, want))
-
-
-@cases("scaled_morphometry", "vip_score", "ashift")
-@both
-def morphometry(fn, dtype, Z, ctx):
-    from test_gpu_morphometry import compare_morphometry
-    kw = T.golden_kw("morphometry.npz", fn)
-    if fn == "scaled_morphometry":
-        ref = lambda got: compare_morphometry(got, mnp.scaled_morphometry(Z, **kw), (ctx,))      # noqa: E731
-    else:
-        ref = lambda got: assert_exact(got, getattr(mnp, fn)(Z, **kw), ctx)                     # noqa: E731
-    yield dict(fn=lambda Zt: F(fn)(Zt, **kw), inputs=[Z], ctx=(ctx, kw), reference=ref)
-
-
-@cases("raster_stats", "rmse", "normalize")
-@both
-def statistics(fn, dtype, Z, ctx):
-    if fn == "raster_stats":
-        yield dict(fn=lambda Zt: F("raster_stats")(Zt), inputs=[Z], ctx=ctx, reference=lambda got: T.stats_match(got, Z, ctx))
-    elif fn == "rmse":
-        yield dict(fn=lambda Zt: F("rmse")(Zt), inputs=[Z], ctx=ctx,
-                   reference=lambda got: (got.dtype == Z.dtype and got == rn.rmse(Z)) or pytest.fail("rmse %r" % (ctx,)))
-    else:
-        xr, yr = ['min', 'median', 'max'], [-1, 0, 1]
-        yield dict(fn=lambda Zt: F("normalize")(Zt, xr, yr), inputs=[Z], ctx=ctx,
-                   reference=lambda got: assert_exact(got, rn.normalize(Z, xr, yr), ctx))
-
-
-@cases("colortable_shade", "swiss_shading", "brassel_atmospheric_perspective")
-@both
-def relief(fn, dtype, Z, ctx):
-    import neilpy_amd as na
-    G = golden("relief.npz")
-    if fn == "brassel_atmospheric_perspective":
-        Hs = np.round(255 * np.random.default_rng(8).uniform(0, 1, size=Z.shape)).astype(np.uint8)
-        kw = dict(k=2.303, C2=0.41)
-        yield dict(fn=lambda Ht, Zt: F(fn)(Ht, Zt, **kw), inputs=[Hs, Z], ctx=(ctx, "u8"),
-                   reference=T.brassel_reference(Hs, Z, kw, (ctx, "u8")))
-        return
-    H = na.hillshade(Z, 2)                                   # the device's own shade, made on the default stream beforehand
-    table = "lut_ghc" if fn == "colortable_shade" else "lut_swiss"
-    want = rn.table3(G[table])[np.zeros(Z.shape, int), H]    # np.min / np.max of a raster with a NaN
-    call = (lambda Zt, lt: F("colortable_shade")(Zt, lt, 2)) if fn == "colortable_shade" else \
-        (lambda Zt, lt: F("swiss_shading")(Zt, 2, lut=lt))
-    yield dict(fn=call, inputs=[Z, G[table]], ctx=(ctx, table),
-               reference=lambda got: (got.dtype == np.uint8 and np.array_equal(got, want)) or pytest.fail(
-                   "%s %r: %d cells differ" % (fn, ctx, int((got != want).sum()))))
-
-
-@cases("progressive_filter")
-def progressive_filter(_):
-    """(70, 300), finite: one window list per route the plan reports for it, as test_progressive_filter_routes draws them"""
-    for dtype in (F32, F64):
-        Z = T.pf_raster(PF_SHAPE, dtype, False)
-        routes = T.pf_routes(PF_SHAPE, dtype, False)
-        for win, impl in sorted(set(routes.values())):
-            w = np.asarray(win)
-            want_m, want_w = mn.progressive_filter(Z, w, 1, .15, return_when_dropped=True)
-            yield dict(fn=lambda Zt, w=w, impl=impl: F("progressive_filter")(Zt, w, 1, .15, return_when_dropped=True, impl=impl),
-                       inputs=[Z], ctx=(PF_SHAPE, np.dtype(dtype).name, win, impl),
-                       reference=lambda got, m=want_m, n=want_w: (np.array_equal(got[0], m) and np.array_equal(got[1], n)) or
-                       pytest.fail("progressive_filter: mask %d, when %d cells differ" % (
-                           int((got[0] != m).sum()), int((got[1] != n).sum()))))
-
-
-@cases(*T.DISK)
-def disk(fn):
-    for dtype in (F32, F64):
-        Z = T.pf_raster(PF_SHAPE, dtype, False)
-        r = 17
-        want = {"erosion": lambda: mn.erosion(Z, r, "rows"), "dilation": lambda: mn.dilation(Z, r, "rows"),
-                "opening": lambda: mn.dilation(mn.erosion(Z, r, "rows"), r, "rows")}[fn]()
-        c = (PF_SHAPE, np.dtype(dtype).name, r, fn)
-        yield dict(fn=lambda Zt: F(fn)(Zt, radius=r), inputs=[Z], ctx=c, reference=lambda got, w=want: assert_exact(got, w, c))
-
-
-@cases("create_dem")
-def create_dem(_):
-    from oracle import smrf_oracle as orc
-    x, y, z, _g = load_sample("samp21")
-    want = orc.create_dem(x, y, z, 1, 'min')
-    yield dict(fn=lambda a, b, c: F("create_dem")(a, b, c, 1, 'min'), inputs=[x, y, z], ctx="samp21",
-               reference=lambda got: T.dem_match(got, want, "samp21"))
-
-
-@cases("read_las_xyz")
-def read_las(_):
-    yield T.read_las_case()
-
-
-@cases("inpaint_nearest", "nearest_source")
-def nearest(fn):
-    for dtype in (F32, F64):
-        X = T.holes(SHAPE, dtype, .6, 2)
-        ctx = (SHAPE, np.dtype(dtype).name)
-        if fn == "inpaint_nearest":
-            yield dict(fn=lambda Xt: F("inpaint_nearest")(Xt), inputs=[X], ctx=ctx,
-                       reference=lambda got, X=X: nn.same_bits(got, nn.inpaint_nearest(X)) or pytest.fail("inpaint_nearest"))
-        else:
-            def ref(got, X=X):
-                dist, rc = got
-                index, dist2, _ = nn.feature_transform(np.ascontiguousarray(X))
-                assert dist.dtype == np.float64 and rc.dtype == np.int64 and rc.shape == (2,) + X.shape, ctx
-                assert np.array_equal(rc[0] * X.shape[1] + rc[1], index), ctx
-                assert np.array_equal(dist, np.sqrt(dist2.astype(np.float64))), ctx
-            yield dict(fn=lambda Xt: F("nearest_source")(Xt), inputs=[X], ctx=ctx, reference=ref)
-
-
-@cases("inpaint_nans_by_springs")
-def springs(_):
-    yield T.springs_case((37, 53), 1, .5)
-
-
-@cases("inpaint_nans_by_fda")
-def fda(_):
-    yield T.fda_case()
-
-
-@cases("nearest_points", "chamfer_distance")
-def points(fn):
-    d, n = 2, 257
-    rng = np.random.default_rng(140 + d)
-    q = rng.uniform(-1, 11, (257, d))
-    p = rng.uniform(0, 10, (n, d))
-    if fn == "nearest_points":
-        wd, wi = pn.nearest_points(q, p)
-
-        def ref(got):
-            assert got[0].dtype == np.float64 and got[1].dtype == np.int64
-            bad = np.flatnonzero((got[1] != wi) | (got[0].view(np.uint64) != wd.view(np.uint64)))
-            assert bad.size == 0, (n, d, bad.size, bad[:5])
-        yield dict(fn=lambda qt, pt: F("nearest_points")(qt, pt), inputs=[q, p], ctx=(n, d), reference=ref)
-    else:
-        want = pn.chamfer_distance(q, p)
-        yield dict(fn=lambda qt, pt: F("chamfer_distance")(qt, pt), inputs=[q, p], ctx=(n, d),
-                   reference=lambda got: T.chamfer_close(got, want, n + len(q)))
-
-
-@cases("voxelize")
-def voxelize(_):
-    from test_gpu_voxel import cloud
-    for dtype in (F32, F64):
-        x, y, z = cloud(4000, 77, dtype)
-        kw = dict(ve=33 / 8.0, bottom_fill=False, pad=3, threshold=2)
-        want = vn.voxelize(None, x, y, z, 32, **kw)
-        yield dict(fn=lambda a, b, c: F("voxelize")(None, a, b, c, 32, **kw), inputs=[x, y, z], ctx=(np.dtype(dtype).name, kw),
-                   reference=lambda got, w=want: (got.dtype == bool and got.shape == w.shape and np.array_equal(got, w)) or
-                   pytest.fail("voxelize %r" % (kw,)))
-
-
-@cases("pssm")
-def pssm(_):
-    from oracle import smrf_oracle as orc
-    from test_pssm import G
-    Z = T.raster(T.PSSM_SHAPES[-1], F64)
-    yield dict(fn=lambda Zt: F("pssm")(Zt, 1.5, 2.3, False, False), inputs=[Z], ctx="classes",
-               reference=lambda got: (got.dtype == np.uint8 and np.array_equal(got, orc.pssm_classes(Z, 1.5, 2.3))) or
-               pytest.fail("pssm classes"))
-    yield dict(fn=lambda Zt: F("pssm")(Zt, 1.5, 2.3, True), inputs=[Z], ctx="rgba",
-               reference=lambda got: (got.shape == Z.shape + (4,) and np.array_equal(got, orc.pssm(Z, G["lut_bone"], 1.5, 2.3)))
-               or pytest.fail("pssm rgba"))
-
-
-@cases("smrf")
-def smrf(_):
-    yield T.smrf_case()[0]
-
-
-# run outside GUARDED's names: (case builder, run_streamed options)
-EXTRA = {
-    "smrf_spline": (lambda: T.spline_case((9, 300)), {}),
-    # the band driver posts its exchanges on a stream of its own making: those handles are its own business, the
-    # wait_event / wait_stream wiring to the caller's stream is what the data check sees
-    "sharded": (lambda: T.sharded_case(), dict(own_streams=True)),
-}
-
-
-def _run(case, **opts):
-    return streamed(case["fn"], case["inputs"], name=case.get("name", "?"), ctx=case["ctx"], reference=case["reference"], **opts)
+def run_marked(name, builder):
+    """every ``stream=True`` case ``builder`` yields for ``name``, and at least one"""
+    n = 0
+    for case in builder((name,)):
+        if case["stream"]:
+            streamed(case["fn"], case["inputs"], name=name, ctx=case["ctx"], reference=case["reference"], **OPTIONS.get(name, {}))
+            n += 1
+    assert n >= 1, name
 
 
 @pytest.mark.parametrize("name", GUARDED)
 def test_family(gpu_device, name):
-    n = 0
-    for case in CASES[name]():
-        _run(dict(case, name=name))
-        n += 1
-    assert n >= 1, name
+    run_marked(name, FC.BUILDERS[name])
 
 
-@pytest.mark.parametrize("name", sorted(EXTRA))
+@pytest.mark.parametrize("name", sorted(FC.EXTRA))
 def test_extra(gpu_device, name):
-    build, opts = EXTRA[name]
-    _run(build(), **opts)
+    run_marked(name, FC.EXTRA[name])
 
 
 # ------------------------------------------------------------------------------------------
@@ -369,9 +118,9 @@ def test_numpy_in_numpy_out(gpu_device, shape):
     the pinned staging buffers both ways and their events are recorded on the side stream"""
     from neilpy_amd import _xfer
     from test_gpu_surface import compare
-    Z = T.raster(shape, F32, nan=(shape == SHAPE), seed=7)
+    Z = FC.raster(shape, F32, nan=(shape == SHAPE), seed=7)
     assert (Z.nbytes >= _xfer.SMALL) == (shape != SHAPE) and Z.nbytes < _xfer.SMALL + (64 << 10)
-    kw = T.golden_kw("surface.npz", "slope")
+    kw = FC.golden_kw("surface.npz", "slope")
 
     def ref(got):
         assert isinstance(got, np.ndarray)
@@ -389,13 +138,13 @@ def test_two_streams_share_an_input_and_the_cached_tables(gpu_device):
     import torch
     import neilpy_amd as na
     from guarded import same_bits
-    Z, _ = nan_raster(F64)
-    kw_e = T.golden_kw("surface.npz", "evans_curvature")
-    kw_m = dict(T.golden_kw("morphometry.npz", "scaled_morphometry"), lookup_pixels=1)
+    Z = FC.raster(SHAPE, F64, nan=True, seed=7)
+    kw_e = FC.golden_kw("surface.npz", "evans_curvature")
+    kw_m = dict(FC.golden_kw("morphometry.npz", "scaled_morphometry"), lookup_pixels=1)
     Zd = torch.from_numpy(Z).to(S.DEVICE)
     torch.cuda.synchronize()
-    want_e = T._rebuild(na.evans_curvature(Zd, **sn.decode_kw(kw_e)), T._np)
-    want_m = T._rebuild(na.scaled_morphometry(Zd, **kw_m), T._np)
+    want_e = FC.rebuild(na.evans_curvature(Zd, **sn.decode_kw(kw_e)), FC.to_numpy)
+    want_m = FC.rebuild(na.scaled_morphometry(Zd, **kw_m), FC.to_numpy)
     torch.cuda.synchronize()
     A, B = torch.cuda.Stream(), torch.cuda.Stream()
     sleep = S.delay()
@@ -411,12 +160,12 @@ def test_two_streams_share_an_input_and_the_cached_tables(gpu_device):
         B.wait_event(written)
         got_m = na.scaled_morphometry(buf, **kw_m)
     with torch.cuda.stream(A):
-        got_e = T._rebuild(got_e, T._np)
+        got_e = FC.rebuild(got_e, FC.to_numpy)
     with torch.cuda.stream(B):
-        got_m = T._rebuild(got_m, T._np)
+        got_m = FC.rebuild(got_m, FC.to_numpy)
     torch.cuda.synchronize()
     for tag, got, want in (("evans_curvature", got_e, want_e), ("scaled_morphometry", got_m, want_m)):
-        a, b = list(T._leaves(got)), list(T._leaves(want))
+        a, b = list(FC.leaves(got)), list(FC.leaves(want))
         assert [p for p, _ in a] == [p for p, _ in b], tag
         for (path, u), (_, v) in zip(a, b):
             assert same_bits(u, v), (tag, path)

@@ -15,7 +15,8 @@ W4  inpaint_nans_by_springs, the spline solve and evaluation, nearest_source, to
 Rounds 0..2: thread t runs W((t + r) mod 4).  Round 3: all four run W3 on four different rasters and clouds.  Round 4: all
 four run the progressive filter with four different window lists.  A barrier stands in front of every round; exceptions
 are collected per thread and raised on the main thread; every join has a timeout.  ``api.last_stats`` is a module-level
-dict that reports the process's latest call and is not looked at here.
+dict that reports the process's latest call and is not looked at here.  The rasters, the spline pair and the reading
+of result trees are tests/family_cases.py's, shared with the guarded and the stream module.
 """
 import ctypes as C
 import hashlib
@@ -27,8 +28,8 @@ import threading
 import numpy as np
 import pytest
 
-import test_gpu_guarded as T
 from conftest import ROOT, golden
+from family_cases import holes, leaves, pf_raster, raster, spline_case, to_numpy
 from pf_run import run_pf
 
 pytestmark = pytest.mark.gpu
@@ -51,7 +52,7 @@ def digest(parts):
 
 def host(v):
     """tensors, dicts, tuples and scalars of a result as a flat list of NumPy arrays (read on the current stream)"""
-    return [np.asarray(T._np(x)) for _, x in T._leaves(v) if x is not None]
+    return [np.asarray(to_numpy(x)) for _, x in leaves(v) if x is not None]
 
 
 def dev(a):
@@ -60,7 +61,7 @@ def dev(a):
 
 
 def pf_work(shape, dtype, windows):
-    Zd = dev(T.pf_raster(shape, dtype, False))
+    Zd = dev(pf_raster(shape, dtype, False))
 
     def work():
         mask, when, _planes, route, taken = run_pf(Zd, windows)
@@ -83,7 +84,7 @@ def w3(k=0):
     X = (rng.normal(size=(211 + k, 307)) * 30 + 400).astype(F32 if k % 2 == 0 else F64)
     X[rng.random(X.shape) < 0.02] = np.nan
     Xd = dev(X)
-    Zd = dev(T.raster((67 + k, 131), F64, seed=k))
+    Zd = dev(raster((67 + k, 131), F64, seed=k))
     lut = dev(golden("relief.npz")["lut_ghc"])
     q, p = dev(rng.uniform(-1, 11, (257, 2 + k % 2))), dev(rng.uniform(0, 10, (3000 + 10 * k, 2 + k % 2)))
     x, y, z = (dev(c) for c in cloud(4000 + k, 77 + k, F64))
@@ -96,9 +97,9 @@ def w4():
     import neilpy_amd as na
     from test_gpu_springs import raster as springs_raster
     A = dev(np.array(springs_raster((37, 53), 1, .5)))
-    X = dev(T.holes((67, 131), F32, .6, 2))
-    Zd = dev(T.raster((67, 131), F64, seed=3))
-    case = T.spline_case((9, 300))
+    X = dev(holes((67, 131), F32, .6, 2))
+    Zd = dev(raster((67, 131), F64, seed=3))
+    case = spline_case((9, 300))
     sp = [dev(a) for a in case["inputs"]]
 
     def springs():
@@ -174,7 +175,7 @@ def test_error_text_is_per_thread(gpu_device):
     import torch
     from neilpy_amd import _lib
     lib = _lib.load()
-    Zd = dev(T.pf_raster((70, 300), F32, False))
+    Zd = dev(pf_raster((70, 300), F32, False))
     mask = torch.zeros((70, 300), dtype=torch.uint8, device=Zd.device)
     nbytes = int(lib.smrf_progressive_filter_workspace_bytes(70, 300, 4))
     ws = torch.zeros(nbytes, dtype=torch.uint8, device=Zd.device)

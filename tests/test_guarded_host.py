@@ -195,12 +195,13 @@ def test_a_tensor_allocated_behind_the_harness():
 
 
 def test_every_export_is_guarded_left_out_with_a_reason_or_launches_nothing():
-    """tests/test_gpu_guarded.py classifies every public name of the package: called under the harness, left out with a
-    reason, or launching no kernel.  A family added later cannot go unguarded silently: its names are in none of the lists."""
+    """tests/family_cases.py classifies every public name of the package: built into cases that run under the harness, left
+    out with a reason, or launching no kernel.  A family added later cannot go unguarded silently: its names are in none of
+    the lists, and a name of GUARDED without a builder fails here."""
     import re
     import types
     import neilpy_amd
-    import test_gpu_guarded as T
+    import family_cases as T
     exports = {n for n, v in vars(neilpy_amd).items() if not n.startswith("_") and not isinstance(v, types.ModuleType)}
     lists = (set(T.GUARDED), set(T.LEFT_OUT), set(T.NO_KERNEL))
     assert len(T.GUARDED) == len(lists[0]) and len(T.NO_KERNEL) == len(lists[2])
@@ -208,6 +209,7 @@ def test_every_export_is_guarded_left_out_with_a_reason_or_launches_nothing():
     assert lists[0] | lists[1] | lists[2] == exports, (sorted(exports - lists[0] - lists[1] - lists[2]),
                                                         sorted((lists[0] | lists[1] | lists[2]) - exports))
     assert all(isinstance(r, str) and r for r in T.LEFT_OUT.values())
+    assert set(T.BUILDERS) == lists[0], sorted(set(T.BUILDERS) ^ lists[0])
     # every guarded name is really called: as the literal F("name"), or as F(fn) over one of the three tuples
     src = open(T.__file__.rstrip("c")).read()
     literal = set(re.findall(r'\bF\("(\w+)"\)', src))

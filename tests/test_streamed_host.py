@@ -136,12 +136,14 @@ def test_a_decoy_is_another_draw_of_the_same_values():
 
 
 def test_every_guarded_export_has_a_stream_case():
-    """tests/test_gpu_streams.py runs one case table entry per name of test_gpu_guarded.GUARDED (which
-    tests/test_guarded_host.py ties to the package's exports): a family added later cannot join without a stream case"""
-    import test_gpu_guarded as T
+    """tests/test_gpu_streams.py runs, per name of family_cases.GUARDED (which tests/test_guarded_host.py ties to the
+    package's exports), the cases that name's builder marks for it, and fails on the GPU where a builder marks none: a
+    family added later cannot join without a stream case"""
+    import family_cases as T
     import test_gpu_streams as M
-    assert set(M.CASES) == set(T.GUARDED), sorted(set(M.CASES) ^ set(T.GUARDED))
+    assert set(T.BUILDERS) == set(T.GUARDED), sorted(set(T.BUILDERS) ^ set(T.GUARDED))
     assert not T.LEFT_OUT                                    # a name left out there needs its written reason here as well
-    assert set(M.EXTRA) == {"smrf_spline", "sharded"} and not set(M.EXTRA) & set(T.GUARDED)
-    src = open(M.__file__.rstrip("c")).read()
-    assert '@pytest.mark.parametrize("name", GUARDED)' in src
+    assert set(T.EXTRA) == {"smrf_spline", "sharded"} and not set(T.EXTRA) & set(T.GUARDED)
+    marks = {f: [m.args for m in getattr(M, f).pytestmark if m.name == "parametrize"] for f in ("test_family", "test_extra")}
+    assert marks == {"test_family": [("name", T.GUARDED)], "test_extra": [("name", sorted(T.EXTRA))]}, marks
+    assert set(M.OPTIONS) <= set(T.EXTRA)
