@@ -242,6 +242,16 @@ int open_flag_api(const T* last, T* opened, uint8_t* mask, uint8_t* when, double
   return RingFn<T>::call(a, SMRF_RING_FUSED_OPEN, (hipStream_t)stream);
 }
 
+// a chained launch whose surfaces, thresholds and flags `c` holds, on a row band
+template <typename T>
+int chain_launch(int pat, ChainArgs<T> c, int img_rows, int cols, int64_t ld, int in_row0, int in_rows, int out_row0, int out_rows,
+                 hipStream_t stream) {
+  set_band(c, img_rows, cols, ld, in_row0, in_rows, out_row0, out_rows);
+  c.seg = smrf_sw().ring_seg;
+  if constexpr (sizeof(T) == 4) return smrf_chain_f32(pat, c, stream);
+  else return smrf_chain_f64(pat, c, stream);
+}
+
 // several consecutive small windows on a row band in ONE launch (morph_chain.h), the row-band form of what
 // progressive_filter_api does on a whole raster
 template <typename T>
@@ -262,11 +272,7 @@ int chain_flag_api(const T* last, T* opened, uint8_t* mask, uint8_t* when, const
   ChainArgs<T> c{};
   c.in = last; c.out = opened; c.mask = mask; c.when = when;
   for (int k = 0; k < n; ++k) { c.thr[k] = thr[k]; c.widx[k] = widx[k]; }
-  set_band(c, img_rows, cols, ld, in_row0, in_rows, out_row0, out_rows);
-  c.seg = smrf_sw().ring_seg;
-  c.dense0 = 0;
-  if constexpr (sizeof(T) == 4) return smrf_chain_f32(pat, c, (hipStream_t)stream);
-  else return smrf_chain_f64(pat, c, (hipStream_t)stream);
+  return chain_launch(pat, c, img_rows, cols, ld, in_row0, in_rows, out_row0, out_rows, (hipStream_t)stream);
 }
 
 // which windows of this host thread's latest progressive_filter call took the incremental erosion (smrf_pf_ero_inc_windows)
@@ -285,12 +291,9 @@ int progressive_filter_api(const T* Z, int rows, int cols, const int32_t* window
     if (windows[i] < 0) return smrf_fail(SMRF_E_ARG, "negative window %d", windows[i]);
   const size_t plane = (size_t)rows * cols;
   T* E = reinterpret_cast<T*>(ws);
-  // Three planes whose roles rotate: pe holds the latest two-pass window's eroded surface, pl the surface `last` (-1: Z),
-  // and a launch writes its opened surface (the incremental erosion: its eroded one) into a plane that is neither.  After a
-  // folded window (smrf_pf_fold) pe still holds the window BEFORE's eroded surface.
+  // Three planes; which of them a launch reads and writes is the plan's business (smrf_pf_steps; kPfPlaneZ is the caller's raster)
   T* P[3] = {E, E + plane, E + 2 * plane};
-  int pe = 0, pl = -1;
-  auto spare = [&]() { for (int k = 0; k < 3; ++k) if (k != pe && k != pl) return k; return 0; };
+  auto at = [&](int k) -> const T* { return k == kPfPlaneZ ? Z : P[k]; };
   // The first window's flag step writes every mask / when byte (DiskArgs::dense), so the planes are not cleared first:
   // one coalesced byte per cell instead of a memset pass plus scattered single-byte stores (window 0 flags the most cells)
   if (nwin == 0) {
@@ -298,20 +301,24 @@ int progressive_filter_api(const T* Z, int rows, int cols, const int32_t* window
     if (when) SMRF_HIP_CHECK(hipMemsetAsync(when, 0, plane, stream));
   }
   // Which launch every window takes is decided once, here, by smrf_pf_route (pf_route.h: small disks as one fused opening, runs
-  // of them as one chained launch, the large ones as two ring passes whose erosion may come from the previous window's); the
-  // loop below executes that plan.  route / pattern: one call-local buffer; the incremental-erosion flags are what
-  // smrf_pf_ero_inc_windows reports.
+  // of them as one chained launch, the large ones as two ring passes whose erosion may come from the previous window's),
+  // smrf_pf_fold marks the windows whose erosion is taken inside their dilation pass, and smrf_pf_steps lists the launches with
+  // their planes; the loop below executes that list.  route / pattern: one call-local buffer; the incremental-erosion flags are
+  // what smrf_pf_ero_inc_windows reports.
   const SmrfSwitches& sw = smrf_sw();
   SmrfPfRules rules{(int)sizeof(T), sw.fused, sw.chain, sw.ero_inc, impl, nan_aware > 0, 0, sw.dil_cross};
   std::vector<int32_t> plan_buf((size_t)2 * nwin);
   int32_t* const route = plan_buf.data();
   int32_t* const pattern = route + nwin;
   g_ero_inc_taken.assign((size_t)nwin, 0);
-  std::vector<uint8_t> fold((size_t)nwin, 0);              // smrf_pf_fold: windows whose erosion is taken inside their dilation pass
+  std::vector<uint8_t> fold((size_t)nwin, 0);
+  std::vector<SmrfPfStep> steps((size_t)2 * nwin);
+  int nsteps = 0;
   auto make_plan = [&](int with_nan) {
     rules.nan_aware = with_nan;
     smrf_pf_route(rules, windows, nwin, rows, (long long)plane, route, g_ero_inc_taken.data(), pattern);
     smrf_pf_fold(rules, windows, route, g_ero_inc_taken.data(), nwin, fold.data());
+    nsteps = smrf_pf_steps(windows, route, g_ero_inc_taken.data(), fold.data(), pattern, nwin, steps.data());
   };
   make_plan(nan_aware > 0);
   // nan_aware < 0: the library finds out itself.  When the plan for a raster without NaN starts with a chained / table-free
@@ -319,11 +326,11 @@ int progressive_filter_api(const T* Z, int rows, int cols, const int32_t* window
   // NaN, the flag is read back after it (the one synchronising readback a separate count would need as well), and in the rare
   // case it is set the plan is made again for a raster with NaNs (scipy's NaN rule lives in the two-pass kernels only) and the
   // call starts over.  Otherwise: one count pass first.  The flag is the first word of the workspace's E plane, which nothing
-  // touches before the first two-pass window's erosion (chained / fused launches never write plane pe = 0) - no allocation on
-  // this path.
+  // touches before the first two-pass window's erosion (smrf_pf_steps: chained / fused launches never write plane 0 before it)
+  // - no allocation on this path.
   unsigned* d_nan = nullptr;
   if (nan_aware < 0) {
-    if (nwin > 0 && route[0] == SMRF_ROUTE_CHAIN && sw.nan_ride != 0) {   // SMRF_NAN_RIDE=0: always a separate count pass (A/B runs)
+    if (nsteps > 0 && steps[0].kind == kPfStepChain && sw.nan_ride != 0) {   // SMRF_NAN_RIDE=0: always a separate count pass (A/B runs)
       d_nan = reinterpret_cast<unsigned*>(E);
       SMRF_HIP_CHECK(hipMemsetAsync(d_nan, 0, sizeof(unsigned), stream));
       nan_aware = 0;
@@ -357,25 +364,18 @@ int progressive_filter_api(const T* Z, int rows, int cols, const int32_t* window
     SMRF_HIP_CHECK(e);
     return SMRF_OK;
   };
-  const T* last = Z;
-  for (int i = 0; i < nwin;) {
-    const int r = windows[i];
-    const int po = spare();
-    T* opened = P[po];
-    switch (route[i]) {
-      case SMRF_ROUTE_CHAIN: {   // windows i .. i + len - 1 in ONE launch that reads `last` and writes the last window's opening (morph_chain.h)
-        const int len = smrf_chain_length(pattern[i]);
+  for (int s = 0; s < nsteps;) {
+    const SmrfPfStep& st = steps[(size_t)s];
+    const int i = st.win, r = windows[i];
+    T* const dst = P[st.dst];
+    switch (st.kind) {
+      case kPfStepChain: {       // windows i .. i + len - 1 in ONE launch that reads `last` and writes the last window's opening (morph_chain.h)
         ChainArgs<T> c{};
-        c.in = last; c.out = opened; c.mask = mask; c.when = when;
-        for (int k = 0; k < len; ++k) { c.thr[k] = thr[i + k]; c.widx[k] = i + k; }
-        set_band(c, rows, cols, cols, 0, rows, 0, rows);
-        c.seg = sw.ring_seg;
-        c.dense0 = i == 0;
+        c.in = at(st.src); c.out = dst; c.mask = mask; c.when = when;
+        for (int k = 0; k < st.len; ++k) { c.thr[k] = thr[i + k]; c.widx[k] = i + k; }
+        c.dense0 = st.dense;
         c.nan_flag = d_nan;                                  // not NULL: the speculative first launch
-        int crc;
-        if constexpr (sizeof(T) == 4) crc = smrf_chain_f32(pattern[i], c, stream);
-        else crc = smrf_chain_f64(pattern[i], c, stream);
-        if (crc) return crc;
+        if (int rc = chain_launch(st.pattern, c, rows, cols, cols, 0, rows, 0, rows, stream)) return rc;
         if (d_nan) {                                         // did it meet a NaN?
           unsigned h = 0;
           SMRF_HIP_CHECK(hipMemcpyAsync(&h, d_nan, sizeof(h), hipMemcpyDeviceToHost, stream));
@@ -384,59 +384,45 @@ int progressive_filter_api(const T* Z, int rows, int cols, const int32_t* window
           if (h) {                                           // its results are discarded: start over with scipy's NaN rule
             nan_aware = 1;
             make_plan(1);
-            continue;                                        // i is still 0, the planes' roles and `last` as at the start
+            continue;                                        // s is still 0
           }
         }
-        if (nwin > 1) { last = opened; pl = po; }
-        for (int k = 0; k < len; ++k)                        // the chain's time lands on its first window, the others read ~0
-          if (int rc = window_done(i + k)) return rc;
-        i += len;
         break;
       }
-      case SMRF_ROUTE_FUSED:     // opening + flag in ONE launch, the eroded surface never leaves the CU (morph_fused.h; 10 instead of 22 B/cell in fp32)
-        if (int rc = open_flag_api<T>(last, opened, mask, when, thr[i], i, rows, cols, cols, 0, rows, 0, rows, r, stream_, i == 0)) return rc;
-        if (nwin > 1) { last = opened; pl = po; }
-        if (int rc = window_done(i)) return rc;
-        ++i;
+      case kPfStepFused:         // opening + flag in ONE launch, the eroded surface never leaves the CU (morph_fused.h; 10 instead of 22 B/cell in fp32)
+        if (int rc = open_flag_api<T>(at(st.src), dst, mask, when, thr[i], i, rows, cols, cols, 0, rows, 0, rows, r, stream_, st.dense)) return rc;
         break;
-      default:                   // two passes: ring or direct kernels by `impl`, the copy kernel for radius 0
-        if (fold[(size_t)i] == kPfFoldCross) {
-          // a rim-free window (P_R empty: e_R = erode(e_{R-1}, cross)) launches no erosion: its dilation pass reads e_{R-1} from
-          // P[pe], takes the cross on load (morph_ring.h, ring_cross_kernel) and writes opened_R into the spare plane.  P[pe] keeps
-          // e_{R-1}: the next window cannot start from it (smrf_pf_fold, kPfFoldAfter) and erodes over it.
-          if constexpr (sizeof(T) == 4) {
-            if (int rc = dilate_cross_flag_f32(P[pe], last, opened, mask, when, thr[i], i, rows, cols, r, stream)) return rc;
-          } else {
-            return smrf_fail(SMRF_E_HIP, "internal: no cross on load at this dtype");
-          }
-          last = opened;
-          pl = po;
-        } else if (smrf_pf_runs_inc(g_ero_inc_taken.data(), fold.data(), i)) {
-          // window R's erosion from window R-1's (morph_incero.h): e_R = min(erode(e_{R-1}, cross), min over the
-          // leftover cells P_R of last).  e_R goes into the spare plane (it held opened_{R-2}), then opened_R goes over e_{R-1}
-          if constexpr (sizeof(T) == 4) {
-            if (int rc = smrf_inc_erode_f32(P[pe], last, P[po], rows, cols, cols, r, nt_rule<T>(rows, cols), stream)) return rc;
-          } else {
-            return smrf_fail(SMRF_E_HIP, "internal: no incremental erosion at this dtype");
-          }
-          opened = P[pe];
-          if (int rc = dilate_flag_api<T>(P[po], last, opened, mask, when, thr[i], i, rows, cols, cols, 0, rows, 0, rows, r,
-                                          nan_aware, impl, stream_, 0))
-            return rc;
-          last = opened;
-          pl = pe;
-          pe = po;
+      case kPfStepErode:         // ring or direct kernel by `impl`, the copy kernel for radius 0
+        if (int rc = disk_filter_api<T>(at(st.src), dst, rows, cols, cols, 0, rows, 0, rows, r, 0, nan_aware, impl, stream_)) return rc;
+        break;
+      case kPfStepIncErode:      // window R's erosion from window R-1's (morph_incero.h): e_R = min(erode(e_{R-1}, cross), min
+                                 // over the leftover cells P_R of last)
+        if constexpr (sizeof(T) == 4) {
+          if (int rc = smrf_inc_erode_f32(at(st.src), at(st.aux), dst, rows, cols, cols, r, nt_rule<T>(rows, cols), stream)) return rc;
+          break;
         } else {
-          if (int rc = disk_filter_api<T>(last, P[pe], rows, cols, cols, 0, rows, 0, rows, r, 0, nan_aware, impl, stream_)) return rc;
-          if (int rc = dilate_flag_api<T>(P[pe], last, opened, mask, when, thr[i], i, rows, cols, cols, 0, rows, 0, rows, r,
-                                          nan_aware, impl, stream_, i == 0))
-            return rc;
-          if (nwin > 1) { last = opened; pl = po; }           // neilpy.py:1675-1676
+          return smrf_fail(SMRF_E_HIP, "internal: no incremental erosion at this dtype");
         }
-        if (int rc = window_done(i)) return rc;
-        ++i;
+      case kPfStepDilate:
+        if (int rc = dilate_flag_api<T>(at(st.src), at(st.aux), dst, mask, when, thr[i], i, rows, cols, cols, 0, rows, 0, rows, r,
+                                        nan_aware, impl, stream_, st.dense))
+          return rc;
         break;
+      case kPfStepDilateCross:   // a rim-free window (P_R empty: e_R = erode(e_{R-1}, cross)) launches no erosion: its dilation pass reads
+                                 // e_{R-1} and takes the cross on load (morph_ring.h, ring_cross_kernel)
+        if constexpr (sizeof(T) == 4) {
+          if (int rc = dilate_cross_flag_f32(at(st.src), at(st.aux), dst, mask, when, thr[i], i, rows, cols, r, stream)) return rc;
+          break;
+        } else {
+          return smrf_fail(SMRF_E_HIP, "internal: no cross on load at this dtype");
+        }
+      default:
+        return smrf_fail(SMRF_E_HIP, "internal: unknown step kind %d", st.kind);
     }
+    if (st.closes)                                           // a chain's time lands on its first window, the others read ~0
+      for (int k = 0; k < st.len; ++k)
+        if (int rc = window_done(i + k)) return rc;
+    ++s;
   }
   return finish();
 }

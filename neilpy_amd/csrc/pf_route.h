@@ -1,8 +1,10 @@
 // Which launch every window of progressive_filter takes: the whole rule, as tables and one pure function (smrf_pf_route).
-// The whole-raster driver (morph.hip, progressive_filter_api) executes the plan this function makes, and the row-band driver
-// (neilpy_amd/sharded.py) asks the same function through smrf_pf_plan of the C ABI.  Plain C++, no HIP: included by
-// smrf_common.h and compiled on its own by tests/test_pf_route_host.py.  smrf_pf_fold, a second pure function after it, marks the
-// two-pass windows whose erosion is taken inside their dilation pass (tests/test_pf_fold_host.py).
+// The row-band driver (neilpy_amd/sharded.py) asks that function through smrf_pf_plan of the C ABI.  smrf_pf_fold, a second pure
+// function after it, marks the two-pass windows whose erosion is taken inside their dilation pass, and smrf_pf_steps, the third,
+// turns the three lists into the launches of a whole-raster call, each with the workspace planes it reads and writes: the
+// whole-raster driver (morph.hip, progressive_filter_api) is a flat loop over that list.  Plain C++, no HIP: included by
+// smrf_common.h and compiled on its own by tests/pf_host.py for tests/test_pf_route_host.py, test_pf_fold_host.py and
+// test_pf_steps_host.py.
 #pragma once
 #include <cstdint>
 
@@ -219,3 +221,61 @@ inline void smrf_pf_fold(const SmrfPfRules& k, const int32_t* windows, const int
 }
 // window i's erosion comes from inc_erode_kernel: the route's flag, unless the window is folded or follows a folded one
 inline bool smrf_pf_runs_inc(const uint8_t* ero_inc, const uint8_t* fold, int i) { return ero_inc[i] != 0 && fold[i] == kPfFoldNone; }
+
+// ------------------------------------------------------------------------------------------
+// the launches of a whole-raster call, in order, each with its planes
+// ------------------------------------------------------------------------------------------
+// The workspace is three planes, 0 .. 2; kPfPlaneZ is the caller's raster, kPfPlaneNone "the launch has no such operand".
+//   kind               launches                                                  src          aux    dst
+//   kPfStepChain       smrf_chain_f32 / f64(pattern), windows win .. win+len-1   last         -      spare
+//   kPfStepFused       fused opening + flag                                      last         -      spare
+//   kPfStepErode       erosion by impl (ring, direct, the radius-0 copy)         last         -      pe
+//   kPfStepIncErode    smrf_inc_erode_f32                                        e_{R-1}: pe  last   spare
+//   kPfStepDilate      dilation + flag by impl                                   e_R          last   spare; after an inc-erode the old pe
+//   kPfStepDilateCross ring_cross_kernel                                         e_{R-1}: pe  last   spare
+// `last` is the surface the window is compared with (Z, then the previous window's opening), pe the plane of the latest written
+// erosion, spare the lowest plane that holds neither.  closes: the step ends its window (a chain: all len of them) - the route
+// report and the timing event belong there.  dense: the step writes every mask / when byte: the closing step of window 0.
+constexpr int kPfStepChain = 0, kPfStepFused = 1, kPfStepErode = 2, kPfStepIncErode = 3, kPfStepDilate = 4, kPfStepDilateCross = 5;
+constexpr int kPfPlaneZ = -1, kPfPlaneNone = -2;
+struct SmrfPfStep { int kind, win, len, src, aux, dst, dense, closes, pattern; };
+
+// After smrf_pf_route and smrf_pf_fold: steps[] (2n entries, the caller's) gets the call's launches, the count is returned.
+// The roles rotate.  The plain two passes write e_R into pe and opened_R into the spare plane.  The incremental erosion needs
+// e_{R-1} beside `last`: e_R goes into the spare plane (it held opened_{R-2}), then opened_R goes over e_{R-1}.  A folded window
+// writes only opened_R and leaves e_{R-1} in pe, which the next window's ring erosion overwrites.  Chained and fused launches
+// leave pe alone, so plane 0 stays untouched until the first erosion (the first word of it is the NaN flag of a speculative
+// first chain), and the workspace ends with the last window's opened surface beside the latest erosion written.
+// tests/test_pf_steps_host.py replays the list on labelled planes.
+inline int smrf_pf_steps(const int32_t* windows, const int32_t* route, const uint8_t* ero_inc, const uint8_t* fold,
+                         const int32_t* pattern, int n, SmrfPfStep* steps) {
+  (void)windows;   // (a step names its window, the driver reads the radius there)
+  int pe = 0, pl = kPfPlaneZ, m = 0;
+  for (int i = 0; i < n;) {
+    int po = 0;
+    while (po == pe || po == pl) ++po;
+    int len = 1;
+    if (route[i] == kPfRouteChain) {
+      len = smrf_chain_length(pattern[i]);
+      steps[m++] = {kPfStepChain, i, len, pl, kPfPlaneNone, po, i == 0, 1, pattern[i]};
+      pl = po;
+    } else if (route[i] == kPfRouteFused) {
+      steps[m++] = {kPfStepFused, i, 1, pl, kPfPlaneNone, po, i == 0, 1, -1};
+      pl = po;
+    } else if (fold[i] == kPfFoldCross) {
+      steps[m++] = {kPfStepDilateCross, i, 1, pe, pl, po, 0, 1, -1};
+      pl = po;
+    } else if (smrf_pf_runs_inc(ero_inc, fold, i)) {
+      steps[m++] = {kPfStepIncErode, i, 1, pe, pl, po, 0, 0, -1};
+      steps[m++] = {kPfStepDilate, i, 1, po, pl, pe, 0, 1, -1};
+      pl = pe;
+      pe = po;
+    } else {
+      steps[m++] = {kPfStepErode, i, 1, pl, kPfPlaneNone, pe, 0, 0, -1};
+      steps[m++] = {kPfStepDilate, i, 1, pe, pl, po, i == 0, 1, -1};
+      pl = po;
+    }
+    i += len;
+  }
+  return m;
+}

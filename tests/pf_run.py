@@ -1,8 +1,6 @@
 """progressive_filter through the C ABI with everything the routing tests look at (shared by test_gpu_ero_inc.py and
 test_gpu_incero_edges.py), and the rule of csrc/pf_route.h for which windows take the incremental erosion, restated."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 
@@ -44,11 +42,8 @@ def run_pf(Zd, windows, nan_aware=-1, impl=0):
 
 def adopted_radii():
     """kEroIncAdoptF32 of csrc/ero_inc_adopt.inc: what SMRF_ERO_INC=1 (the default) takes"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    inc = open(os.path.join(root, "neilpy_amd", "csrc", "ero_inc_adopt.inc")).read()
-    adopt = [int(v) for v in re.search(r"kEroIncAdoptF32\[65\] = \{(.*?)\}", inc, re.S).group(1).replace("\n", " ").split(",")]
-    assert len(adopt) == 65
-    return adopt
+    from pf_host import table
+    return table("kEroIncAdoptF32", "ero_inc_adopt.inc")
 
 
 def inc_rule(windows, route, mode, fp32=True):

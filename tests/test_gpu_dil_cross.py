@@ -11,6 +11,7 @@ import pytest
 
 import morph_numpy as mn
 from conftest import switch
+import pf_host
 from pf_run import run_pf
 from test_gpu_incero_edges import holds, rough, same, value_raster
 
@@ -18,6 +19,10 @@ pytestmark = pytest.mark.gpu
 
 TAKEN = [[15, 16], [20, 21], [14, 15, 16, 17], [35, 36, 37]]
 NOT_TAKEN = [[16], [19, 21]]
+VALUE_LISTS = [[15, 16], [20, 21], [35, 36, 37]]
+TABLE_LISTS = [[15, 16], [20, 21], [35, 36], [15, 16, 17], [20, 21, 22], [35, 36, 37]]
+PLANE_LISTS = [[14, 15, 16, 17], [1, 2, 3, 15, 16], [20, 21], [35, 36, 37], [15, 16, 18, 19]]
+WINDOW_LISTS = TAKEN + NOT_TAKEN + VALUE_LISTS + TABLE_LISTS + PLANE_LISTS   # (tests/test_pf_steps_host.py plans every one of them)
 SHAPES = [(12, 300),                                      # rows far below 2R: every row folded several times
           (97, 257), (150, 513),                          # a strip seam at column 256 and a one-column last strip
           (64, 40)]                                       # narrower than a strip (and than 2R + 1 at R = 21, 36)
@@ -77,7 +82,7 @@ def test_segment_seams_inside_the_raster(nz, gpu_device, monkeypatch, seg, win):
 @pytest.mark.parametrize("kind", ["inf", "inf_block", "constant", "four_levels", "subnormal", "near_max", "negative_zero"])
 def test_value_classes(nz, gpu_device, monkeypatch, kind):
     Zh = value_raster(kind)
-    for win in ([15, 16], [20, 21], [35, 36, 37]):
+    for win in VALUE_LISTS:
         check(Zh, ("value", kind), win, gpu_device, monkeypatch, folds_last=len(win) == 2)
 
 
@@ -88,11 +93,35 @@ def test_the_table_is_the_default_and_keeps_the_last_window(nz, gpu_device, monk
     switch(monkeypatch, "SMRF_DIL_CROSS", None)
     Zh = rough((97, 257), 654)
     Zd = torch.from_numpy(Zh).to(gpu_device)
-    for win in ([15, 16], [20, 21], [35, 36], [15, 16, 17], [20, 21, 22], [35, 36, 37]):
+    for win in TABLE_LISTS:
         rm, rw, er, op = reference(("table",), Zh, win)
         m, w, planes, route, taken = run_pf(Zd, win)
         assert same(m, rm) and same(w, rw), win
         assert holds(planes, er[-1]) and holds(planes, op[-1]), win
+
+
+@pytest.mark.parametrize("win", PLANE_LISTS, ids=lambda w: "w" + "_".join(str(r) for r in w))
+def test_the_workspace_plane_by_plane(nz, gpu_device, monkeypatch, win):
+    """The plan against the execution, at plane level: the call's route and incremental-erosion report, the fold restated
+    (pf_host.restated) and the driver's plane rotation restated (pf_host.parent_steps) say which surface EACH of the three planes
+    holds after the call; each is the reference's, bit for bit.  SMRF_DIL_CROSS 0 / 1 / 2 x SMRF_ERO_INC 0 / 2."""
+    import torch
+    Zh = rough((97, 257), 654)
+    Zd = torch.from_numpy(Zh).to(gpu_device)
+    rm, rw, er, op = reference(("table",), Zh, win)
+    surfaces = {"e": [torch.from_numpy(a).to(gpu_device) for a in er], "o": [torch.from_numpy(a).to(gpu_device) for a in op]}
+    for cross in (0, 1, 2):
+        for inc_mode in (0, 2):
+            switch(monkeypatch, "SMRF_DIL_CROSS", cross)
+            switch(monkeypatch, "SMRF_ERO_INC", inc_mode)
+            m, w, planes, route, taken = run_pf(Zd, win)
+            fold, _ = pf_host.restated(dict(windows=win, dil_cross=cross), route, taken)
+            labels = pf_host.replay(win, route, fold, pf_host.parent_steps(win, route, taken, fold))
+            assert sum(lab != "junk" for lab in labels) == (3 if len(win) > 1 else 2), (cross, inc_mode, win, labels)
+            for k, lab in enumerate(labels):
+                if lab != "junk":
+                    assert torch.equal(planes[k], surfaces[lab[0]][lab[1]]), (cross, inc_mode, win, k, labels)
+            assert same(m, rm) and same(w, rw), (cross, inc_mode, win)
 
 
 def test_a_raster_with_one_nan_is_not_taken(nz, gpu_device, monkeypatch):

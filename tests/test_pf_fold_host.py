@@ -1,95 +1,26 @@
-"""csrc/pf_route.h, smrf_pf_fold - which two-pass windows take their erosion inside their dilation pass (cross on load) - compiled
-with g++ as a stand-alone program and asked directly (no GPU), also under the address and undefined-behaviour sanitizers: the
-benchmark plan, the eligibility edges, "no incremental erosion after a folded window", and the invariants of any plan over
-random window lists against the rule restated here."""
+"""csrc/pf_route.h, smrf_pf_fold - which two-pass windows take their erosion inside their dilation pass (cross on load) - asked through
+the stand-alone program of tests/pf_host.py (no GPU), also under the address and undefined-behaviour sanitizers: the benchmark
+plan, the eligibility edges, "no incremental erosion after a folded window", and the invariants of any plan over random window
+lists against the rule restated in pf_host.py."""
 import os
-import random
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "neilpy_amd", "csrc")
-TWO_PASS, FUSED, DIRECT, COPY, CH = 0, 1, 2, 3, 4
-AUTO, RING, DIRECT_IMPL = 0, 1, 2
-NONE, CROSS, AFTER = 0, 1, 2
-RIM_FREE = (16, 21, 36)                                   # the radii from 15 up whose leftover set P_R is empty (ero_inc.inc)
-
-_MAIN = r'''
-#include <cstdio>
-#include <vector>
-#include "pf_route.h"
-// one case per line: elem_size fused chain ero_inc impl nan_aware band dil_cross rows cells n w[0] .. w[n-1]
-// -> one line: n routes, n incremental-erosion flags of the route, n fold values, n "runs the incremental erosion"
-int main() {
-  SmrfPfRules k;
-  int rows, n;
-  long long cells;
-  while (std::scanf("%d %d %d %d %d %d %d %d %d %lld %d", &k.elem_size, &k.fused, &k.chain, &k.ero_inc, &k.impl, &k.nan_aware,
-                    &k.band, &k.dil_cross, &rows, &cells, &n) == 11) {
-    // exactly n entries each, so that the sanitizer build sees any access beyond them
-    std::vector<int32_t> w(n), route(n, -99);
-    std::vector<uint8_t> inc(n, 99), fold(n, 99);
-    for (int i = 0; i < n; ++i)
-      if (std::scanf("%d", &w[i]) != 1) return 2;
-    smrf_pf_route(k, w.data(), n, rows, cells, route.data(), inc.data());
-    const std::vector<int32_t> route0 = route;
-    const std::vector<uint8_t> inc0 = inc;
-    smrf_pf_fold(k, w.data(), route.data(), inc.data(), n, fold.data());
-    if (route != route0 || inc != inc0) return 3;         // the fold leaves the route's two lists alone
-    for (int i = 0; i < n; ++i) std::printf("%d ", route[i]);
-    for (int i = 0; i < n; ++i) std::printf("%d ", (int)inc[i]);
-    for (int i = 0; i < n; ++i) std::printf("%d ", (int)fold[i]);
-    for (int i = 0; i < n; ++i) std::printf("%d ", (int)smrf_pf_runs_inc(inc.data(), fold.data(), i));
-    std::printf("\n");
-  }
-  return 0;
-}
-'''
-
-
-def _compile(tmp, name, extra):
-    src = tmp / "fold.cpp"
-    src.write_text(_MAIN)
-    exe = tmp / name
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall"] + extra + ["-I", CSRC, str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0 and not r.stderr.strip(), r.stderr[-2000:]
-    return str(exe)
+import pf_host
+from pf_host import AFTER, AUTO, CH, CROSS, CSRC, DIRECT_IMPL, FUSED, NONE, RIM_FREE, RING, TWO_PASS, restated, table
+from pf_host import fold_cases as random_cases
 
 
 def ask(exe, cases):
     """cases: dicts with windows and optionally elem, rows, cells, fused, chain, ero_inc, impl, nan, band, dil_cross
     -> [(route, inc, fold, runs_inc)]"""
-    lines = []
-    for c in cases:
-        w = [int(v) for v in c["windows"]]
-        rows = c.get("rows", 512)
-        lines.append(" ".join(str(int(v)) for v in [c.get("elem", 4), c.get("fused", 1), c.get("chain", 1), c.get("ero_inc", 1), c.get("impl", AUTO),
-                                                    c.get("nan", 0), c.get("band", 0), c.get("dil_cross", 1), rows, c.get("cells", rows * rows),
-                                                    len(w)] + w))
-    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True)
-    assert r.returncode == 0 and not r.stderr.strip(), (r.returncode, r.stderr[-3000:])
-    out = r.stdout.splitlines()
-    assert len(out) == len(cases)
-    res = []
-    for c, ln in zip(cases, out):
-        v, n = [int(x) for x in ln.split()], len(c["windows"])
-        assert len(v) == 4 * n
-        res.append((v[:n], v[n:2 * n], v[2 * n:3 * n], v[3 * n:]))
-    return res
+    return [(p.route, p.inc, p.fold, p.runs) for p in pf_host.ask(exe, cases)]
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    return _compile(tmp_path_factory.mktemp("pf_fold"), "fold", [])
-
-
-def table(name, path):
-    inc = open(os.path.join(CSRC, path)).read()
-    v = [int(x) for x in re.search(name + r"\[65\] = \{(.*?)\}", inc, re.S).group(1).replace("\n", " ").split(",")]
-    assert len(v) == 65
-    return v
+    return pf_host.compile(tmp_path_factory.mktemp("pf_fold"))
 
 
 def adopted():
@@ -170,41 +101,6 @@ def test_no_incremental_erosion_after_a_folded_window(exe):
     assert fold == [NONE, CROSS, AFTER, NONE] and runs == [0, 0, 0, 1]
 
 
-def restated(c, route, inc):
-    """the rule, independently: (fold, runs_inc)"""
-    w, n = [int(v) for v in c["windows"]], len(c["windows"])
-    ad, mode = adopted(), c.get("dil_cross", 1)
-    ok = mode != 0 and not c.get("band", 0) and not c.get("nan", 0) and c.get("elem", 4) == 4 and c.get("impl", AUTO) in (AUTO, RING)
-    fold = []
-    for i in range(n):
-        if i and fold[i - 1] == CROSS:
-            fold.append(AFTER)
-            continue
-        take = (ok and i > 0 and route[i] == TWO_PASS and route[i - 1] == TWO_PASS and w[i] == w[i - 1] + 1 and w[i] in RIM_FREE and
-                (mode == 2 or (ad[w[i]] and i + 1 < n)))
-        fold.append(CROSS if take else NONE)
-    return fold, [int(inc[i] and fold[i] == NONE) for i in range(n)]
-
-
-def random_cases(seed, count):
-    rng = random.Random(seed)
-    cases = []
-    for _ in range(count):
-        n = rng.randint(0, 12)
-        w = []
-        while len(w) < n:
-            if rng.random() < .6:                            # a run around a rim-free radius
-                a = rng.choice(RIM_FREE) - rng.randint(0, 3)
-                w += list(range(a, a + rng.randint(1, 5)))
-            else:
-                w.append(rng.choice([0, 1, 2, 3, 5, 9, 14, 15, 16, 21, 36, 64, 65, 70]))
-        rows = rng.choice([12, 300, 5000])
-        cases.append(dict(windows=w[:n], elem=rng.choice([4, 4, 4, 8]), fused=rng.choice([0, 1, 2]), chain=rng.choice([0, 1]),
-                          ero_inc=rng.choice([0, 1, 2]), impl=rng.choice([AUTO, AUTO, RING, DIRECT_IMPL]), nan=int(rng.random() < .2),
-                          band=rng.choice([0, 0, 0, 1, 2]), dil_cross=rng.choice([0, 1, 2, 2]), rows=rows, cells=rows * rng.choice([40, 300, 5000])))
-    return cases
-
-
 def check_invariants(cases, res):
     for c, (route, inc, fold, runs) in zip(cases, res):
         w, n = c["windows"], len(c["windows"])
@@ -229,8 +125,8 @@ def test_invariants_over_random_window_lists(exe):
 
 def test_under_the_sanitizers(tmp_path):
     """the same program built with -fsanitize=address,undefined, on the edges and a random sweep: no report, same answers"""
-    san = _compile(tmp_path, "fold_san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"])
-    plain = _compile(tmp_path, "fold_plain", [])
+    san = pf_host.compile(tmp_path, pf_host.SANITIZE, "fold_san")
+    plain = pf_host.compile(tmp_path, name="fold_plain")
     cases = random_cases(77, 300) + [dict(windows=[], dil_cross=2), dict(windows=[16], dil_cross=2), dict(windows=[15, 16], dil_cross=2),
                                      dict(windows=list(range(1, 51)), rows=16384)]
     res = ask(san, cases)

@@ -1,87 +1,29 @@
-"""csrc/pf_route.h - which launch every window of progressive_filter takes - compiled with g++ and asked directly (no GPU):
-the route lists the GPU tests observe, the size thresholds, the invariants of any plan over a random sweep (also under the
+"""csrc/pf_route.h - which launch every window of progressive_filter takes - asked through the stand-alone program of
+tests/pf_host.py (no GPU): the route lists the GPU tests observe, the size thresholds, the invariants of any plan over a random sweep (also under the
 address and undefined-behaviour sanitizers), and the row-band form against the band rule the driver used to restate."""
 import ctypes as C
 import os
-import random
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "neilpy_amd", "csrc")
-TWO_PASS, FUSED, DIRECT, COPY, CH = 0, 1, 2, 3, 4
-AUTO, RING, DIRECT_IMPL = 0, 1, 2
-Mi = 1 << 20
-# the launches morph_chain.h has kernels for, restated: radii, smallest raster in cells for fp32 / fp64 (None: no kernel)
-PATTERNS = [((1, 2, 3), 0, 0), ((1, 2), 0, 0), ((2, 3), 0, 0), ((4, 5), 20 * Mi, None), ((4,), 0, 0), ((5,), 0, 0), ((6,), 0, None),
-            ((7,), 0, 4 * Mi), ((8,), 0, 16 * Mi), ((9,), 0, None), ((10,), 20 * Mi, None)]
-
-_MAIN = r'''
-#include <cstdio>
-#include <vector>
-#include "pf_route.h"
-// one case per line: elem_size fused chain ero_inc impl nan_aware band rows cells n w[0] .. w[n-1]
-// -> one line: n routes, n incremental-erosion flags, n pattern indices
-int main() {
-  SmrfPfRules k;
-  int rows, n;
-  long long cells;
-  while (std::scanf("%d %d %d %d %d %d %d %d %lld %d", &k.elem_size, &k.fused, &k.chain, &k.ero_inc, &k.impl, &k.nan_aware,
-                    &k.band, &rows, &cells, &n) == 10) {
-    // exactly n entries each, so that the sanitizer build sees any access beyond them
-    std::vector<int32_t> w(n), route(n, -99), pattern(n, -99);
-    std::vector<uint8_t> inc(n, 99);
-    for (int i = 0; i < n; ++i)
-      if (std::scanf("%d", &w[i]) != 1) return 2;
-    smrf_pf_route(k, w.data(), n, rows, cells, route.data(), inc.data(), pattern.data());
-    for (int i = 0; i < n; ++i) std::printf("%d ", route[i]);
-    for (int i = 0; i < n; ++i) std::printf("%d ", (int)inc[i]);
-    for (int i = 0; i < n; ++i) std::printf("%d ", pattern[i]);
-    std::printf("\n");
-  }
-  return 0;
-}
-'''
-
-
-def _compile(tmp, name, extra):
-    src = tmp / "plan.cpp"
-    src.write_text(_MAIN)
-    exe = tmp / name
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall"] + extra + ["-I", CSRC, str(src), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0 and not r.stderr.strip(), r.stderr[-2000:]
-    return str(exe)
+import pf_host
+from pf_host import AUTO, CH, COPY, DIRECT, DIRECT_IMPL, FUSED, PATTERNS, RING, TWO_PASS, Mi
+from pf_host import route_cases as _random_cases
 
 
 @pytest.fixture(scope="module")
 def planner(tmp_path_factory):
-    exe = _compile(tmp_path_factory.mktemp("pf_route"), "plan", [])
+    exe = pf_host.compile(tmp_path_factory.mktemp("pf_route"))
 
     def plans(cases, exe=exe):
         """cases: dicts with elem, windows, rows, cells and optionally fused, chain, ero_inc, impl, nan, band -> [(route, inc, pattern)]"""
-        lines = []
-        for c in cases:
-            w = [int(v) for v in c["windows"]]
-            lines.append(" ".join(str(int(v)) for v in [c["elem"], c.get("fused", 1), c.get("chain", 1), c.get("ero_inc", 1), c.get("impl", AUTO),
-                                                        c.get("nan", 0), c.get("band", 0), c["rows"], c["cells"], len(w)] + w))
-        r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True)
-        assert r.returncode == 0 and not r.stderr.strip(), r.stderr[-3000:]
-        out = r.stdout.splitlines()
-        assert len(out) == len(cases)
-        res = []
-        for c, ln in zip(cases, out):
-            v, n = [int(x) for x in ln.split()], len(c["windows"])
-            assert len(v) == 3 * n
-            res.append((v[:n], v[n:2 * n], v[2 * n:]))
-        return res
+        return [(p.route, p.inc, p.pattern) for p in pf_host.ask(exe, cases)]
     return plans
 
 
 def adopted_radii():
-    from pf_run import adopted_radii as f
-    return f()
+    return pf_host.table("kEroIncAdoptF32", "ero_inc_adopt.inc")
 
 
 def test_route_lists_the_gpu_tests_observe(planner):
@@ -149,24 +91,6 @@ def test_routes_without_small_disk_kernels(planner):
     assert got == [[FUSED] * 2, [CH, CH + 1], [FUSED], [CH], [FUSED, CH, CH + 1], [CH, CH + 1, CH + 2], [FUSED] * 2]
 
 
-def _random_cases(count, seed):
-    rnd = random.Random(seed)
-    cases = []
-    for _ in range(count):
-        n = rnd.randint(1, 12)
-        if rnd.random() < 0.6:                              # runs of consecutive radii, as real calls have them
-            w, r = [], rnd.randint(0, 66)
-            while len(w) < n:
-                w.append(min(r, 70))
-                r = r + 1 if rnd.random() < 0.8 else rnd.randint(0, 70)
-        else:
-            w = [rnd.randint(0, 70) for _ in range(n)]
-        cases.append(dict(elem=rnd.choice((4, 8)), windows=w, rows=rnd.randint(1, 40000), cells=rnd.choice((1, 3 * Mi, 4 * Mi, 16 * Mi, 20 * Mi - 1, 20 * Mi,
-                          rnd.randint(1, 1 << 30), 1 << 40)), fused=rnd.choice((0, 1, 1, 2)), chain=rnd.choice((0, 1, 1)), ero_inc=rnd.choice((0, 1, 2)),
-                          impl=rnd.choice((AUTO, AUTO, RING, DIRECT_IMPL)), nan=rnd.choice((0, 0, 1)), band=rnd.choice((0, 0, 1, 2))))
-    return cases
-
-
 def _check_invariants(c, route, inc, pat):
     w, n = list(c["windows"]), len(c["windows"])
     i = 0
@@ -213,7 +137,7 @@ def test_plan_invariants_random_and_sanitized(planner, tmp_path):
         _check_invariants(c, route, inc, pat)
     kinds = {r for route, _, _ in got for r in route}
     assert {TWO_PASS, FUSED, DIRECT, COPY, CH, CH + 1, CH + 2} <= kinds and any(any(inc) for _, inc, _ in got)
-    san = _compile(tmp_path, "plan_san", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+    san = pf_host.compile(tmp_path, pf_host.SANITIZE, "plan_san")
     assert planner(cases, exe=san) == got
 
 
