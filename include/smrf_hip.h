@@ -51,6 +51,13 @@
  *   - return value: 0 on success, a negative SMRF_E_* code on failure; smrf_last_error() gives
  *     a human-readable message for the calling thread.  No exceptions cross the boundary.
  *   - rasters are row-major, row 0 = north, `ld` = elements between consecutive rows.
+ *   - a caller's data pointer (rasters, clouds, tables, outputs) needs the alignment of its element and nothing
+ *     wider: any row or element slice of an array is valid input, and every plane is dense (contiguous but for `ld`).
+ *     The one exception says so and refuses: smrf_voxel_expand writes d_out in dwords and returns SMRF_E_ARG for a
+ *     d_out that is not 4-byte aligned.  A workspace is different: the library lays its parts out at multiples of
+ *     256 bytes from the workspace's base and relies on the base being 256-byte aligned, as hipMalloc's and torch's
+ *     allocations are, for the alignment of every part's element (8 bytes at the most).  Allocate
+ *     *_workspace_bytes(...) bytes with either and pass the allocation's own base.
  *   - there is no CPU fallback: without a HIP device every compute entry returns SMRF_E_HIP.
  */
 #ifndef SMRF_HIP_H

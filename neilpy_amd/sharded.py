@@ -372,7 +372,7 @@ def progressive_filter_sharded(Z_band, img_rows, windows, thresholds, *, rank=No
     # band holds a NaN, as the single-device path decides with one count
     nan_aware = 0
     if hasattr(ops, "has_nan"):
-        nan_aware = int(bool(ops.has_nan(Z_band)))
+        nan_aware = int(bool(ops.has_nan(ext[0][b0 - e0:b1 - e0])))      # the band's contiguous copy: Z_band may be any view
         if comm.live:
             nan_aware = comm.reduced(nan_aware, torch.int32, "MAX", dev)
     kw = {"nan_aware": nan_aware} if nan_aware else {}
