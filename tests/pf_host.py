@@ -1,7 +1,8 @@
 """csrc/pf_route.h on the host, for tests/test_pf_route_host.py, test_pf_fold_host.py and test_pf_steps_host.py: one stand-alone
 program that asks smrf_pf_route, smrf_pf_fold and smrf_pf_steps one case per line, its build, the tables and random window
 lists the three modules share, and the driver's plane rotation as it stood before smrf_pf_steps, restated with a symbolic replay
-(tests/test_gpu_dil_cross.py holds the workspace of a real call against that replay, plane by plane)."""
+(tests/test_gpu_dil_cross.py holds the workspace of a real call against that replay, plane by plane, on the window lists of
+tests/window_cases.py)."""
 import os
 import random
 import re

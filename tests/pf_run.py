@@ -1,8 +1,12 @@
-"""progressive_filter through the C ABI with everything the routing tests look at (shared by test_gpu_ero_inc.py and
-test_gpu_incero_edges.py), and the rule of csrc/pf_route.h for which windows take the incremental erosion, restated."""
+"""progressive_filter through the C ABI with everything the routing tests look at, the rule of csrc/pf_route.h for which
+windows take the incremental erosion, restated, and the comparisons of a call against the independent reference
+(tests/morph_numpy.py) that tests/test_gpu_incero_edges.py and tests/test_gpu_dil_cross.py share; their cases are in
+tests/window_cases.py."""
 import ctypes as C
 
 import numpy as np
+
+import morph_numpy as mn
 
 
 def run_pf(Zd, windows, nan_aware=-1, impl=0):
@@ -54,3 +58,67 @@ def inc_rule(windows, route, mode, fp32=True):
     win = [int(v) for v in windows]
     return [int(mode != 0 and fp32 and i > 0 and route[i] == _lib.ROUTE_TWO_PASS and route[i - 1] == _lib.ROUTE_TWO_PASS and
                 win[i] == win[i - 1] + 1 and 16 <= win[i] <= 64 and (mode == 2 or bool(adopt[win[i]]))) for i in range(len(win))]
+
+
+def rotation_plan(windows):
+    """which windows of a list take the incremental erosion under SMRF_ERO_INC=2, judged on the radii alone: every radius
+    15..64 runs as two ring passes on a small raster (test_plane_rotation_across_routes asserts the routes of the call)"""
+    from neilpy_amd import _lib
+    return inc_rule(windows, [_lib.ROUTE_TWO_PASS if 15 <= r <= 64 else _lib.ROUTE_DIRECT for r in windows], 2)
+
+
+# ---- comparisons -------------------------------------------------------------------------------------------------------------
+def bits(a):
+    """the bit patterns of a float array: -0.0 is not +0.0"""
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+
+
+def same(t, a):
+    return np.array_equal(t.cpu().numpy().astype(a.dtype), a)
+
+
+def holds(planes, want):
+    """one of the workspace's three planes is `want`, bit for bit"""
+    got, want = bits(planes.cpu().numpy()), bits(want)
+    return any(np.array_equal(got[k], want) for k in range(3))
+
+
+_references = {}
+
+
+def reference(case, Zh, windows):
+    """(mask, when, eroded surfaces, opened surfaces) of the reference, once per case id and window list.  Of a long list
+    only the last two windows' surfaces are kept (what a workspace can hold); the others are None."""
+    key = (case, tuple(int(r) for r in windows))
+    if key not in _references:
+        m, w, er, op = mn.progressive_filter(Zh, windows, 1, .15, return_when_dropped=True, return_surfaces=True)
+        early = [None] * max(0, len(er) - 2)
+        _references[key] = (m, w, early + er[-2:], early + op[-2:])
+    return _references[key]
+
+
+def pair_failures(r, mask, when, planes, ref, e_restated=None):
+    """windows [r - 1, r] against ref = (mask, when, eroded surfaces, opened surfaces): e_R, opened_R and opened_{R-1} in
+    the workspace's three planes, mask and when_dropped.  Returns the failing (r, what)."""
+    rm, rw, er, op = ref
+    checks = [("e_R", holds(planes, er[1])), ("opened_R", holds(planes, op[1])), ("opened_R-1", holds(planes, op[0])),
+              ("mask", same(mask, rm)), ("when", same(when, rw))]
+    if e_restated is not None:
+        checks.append(("e_R restated", holds(planes, e_restated)))
+    return [(r, what) for what, ok in checks if not ok]
+
+
+def check_pairs(Zh, device, radii=range(16, 65), restated=False):
+    """every R of radii alone: windows [R-1, R], the second one incremental, against the reference (pair_failures); with
+    restated also e_R against the erosion of the opening written out.  Returns the failing (R, what)."""
+    import torch
+    Zd = torch.from_numpy(Zh).to(device)
+    bad = []
+    for r in radii:
+        m, w, planes, route, taken = run_pf(Zd, [r - 1, r])
+        assert taken == [0, 1], (r, taken, route)
+        ref = mn.progressive_filter(Zh, [r - 1, r], 1, .15, return_when_dropped=True, return_surfaces=True)
+        e = mn.erosion(mn.dilation(mn.erosion(Zh, r - 1, "rows"), r - 1, "rows"), r, "rows") if restated else None
+        bad += pair_failures(r, m, w, planes.cpu(), ref, e)
+    return bad

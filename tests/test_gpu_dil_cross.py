@@ -2,30 +2,21 @@
 (R = 16, 21, 36: P_R empty, e_R = erode(e_{R-1}, 5-point cross)) launches no erosion, its dilation pass takes the cross while it
 loads e_{R-1}.  Mask and when_dropped against the independent reference tests/morph_numpy.py, bit for bit, and against the same
 call under SMRF_DIL_CROSS=0, at the shapes where a strip kernel goes wrong: rows far below 2R, strip seams, a one-column last
-strip, a raster narrower than a strip, forced short segments; and on the value classes of tests/test_gpu_incero_edges.py.
+strip, a raster narrower than a strip, forced short segments; and on the value classes of the incremental erosion's tests.
+Window lists, shapes and rasters are in tests/window_cases.py, the comparisons in tests/pf_run.py.
 
 Whether a window was folded shows in the workspace: a folded LAST window leaves e_{R-1} there and no e_R (the planes hold e_{R-1},
 opened_{R-1}, opened_R); a window on its own erosion leaves e_R and has written it over e_{R-1}."""
 import numpy as np
 import pytest
 
-import morph_numpy as mn
-from conftest import switch
 import pf_host
-from pf_run import run_pf
-from test_gpu_incero_edges import holds, rough, same, value_raster
+from conftest import switch
+from pf_run import holds, reference, run_pf, same
+from window_cases import (NOT_TAKEN, PLANE_LISTS, SHAPES, TABLE_LISTS, TAKEN, VALUE_KINDS, VALUE_LISTS, cross_raster, rough,
+                          table_raster, value_raster)
 
 pytestmark = pytest.mark.gpu
-
-TAKEN = [[15, 16], [20, 21], [14, 15, 16, 17], [35, 36, 37]]
-NOT_TAKEN = [[16], [19, 21]]
-VALUE_LISTS = [[15, 16], [20, 21], [35, 36, 37]]
-TABLE_LISTS = [[15, 16], [20, 21], [35, 36], [15, 16, 17], [20, 21, 22], [35, 36, 37]]
-PLANE_LISTS = [[14, 15, 16, 17], [1, 2, 3, 15, 16], [20, 21], [35, 36, 37], [15, 16, 18, 19]]
-WINDOW_LISTS = TAKEN + NOT_TAKEN + VALUE_LISTS + TABLE_LISTS + PLANE_LISTS   # (tests/test_pf_steps_host.py plans every one of them)
-SHAPES = [(12, 300),                                      # rows far below 2R: every row folded several times
-          (97, 257), (150, 513),                          # a strip seam at column 256 and a one-column last strip
-          (64, 40)]                                       # narrower than a strip (and than 2R + 1 at R = 21, 36)
 
 
 @pytest.fixture(scope="module")
@@ -35,22 +26,11 @@ def nz(gpu_device):
     return neilpy_amd
 
 
-_ref = {}
-
-
-def reference(key, Zh, win):
-    """(mask, when, eroded surfaces, opened surfaces) of the reference, once per raster and window list"""
-    k = (key, tuple(win))
-    if k not in _ref:
-        _ref[k] = mn.progressive_filter(Zh, win, 1, .15, return_when_dropped=True, return_surfaces=True)
-    return _ref[k]
-
-
-def check(Zh, key, win, gpu_device, monkeypatch, folds_last):
+def check(Zh, case, win, gpu_device, monkeypatch, folds_last):
     """the call under SMRF_DIL_CROSS=2 and =0: both equal the reference, and the workspace shows which of them folded"""
     import torch
     Zd = torch.from_numpy(Zh).to(gpu_device)
-    rm, rw, er, op = reference(key, Zh, win)
+    rm, rw, er, op = reference(case, Zh, win)
     for mode in ("2", "0"):
         switch(monkeypatch, "SMRF_DIL_CROSS", mode)
         m, w, planes, route, taken = run_pf(Zd, win)
@@ -68,7 +48,7 @@ def check(Zh, key, win, gpu_device, monkeypatch, folds_last):
 @pytest.mark.parametrize("win", TAKEN + NOT_TAKEN, ids=lambda w: "w" + "_".join(str(r) for r in w))
 @pytest.mark.parametrize("shape", SHAPES, ids=["%dx%d" % s for s in SHAPES])
 def test_shapes(nz, gpu_device, monkeypatch, shape, win):
-    check(rough(shape, 300 + shape[0] + shape[1]), ("shape",) + shape, win, gpu_device, monkeypatch, folds_last=win in TAKEN[:2])
+    check(cross_raster(shape), "cross_%dx%d" % shape, win, gpu_device, monkeypatch, folds_last=win in TAKEN[:2])
 
 
 @pytest.mark.parametrize("win", TAKEN, ids=lambda w: "w" + "_".join(str(r) for r in w))
@@ -76,14 +56,14 @@ def test_shapes(nz, gpu_device, monkeypatch, shape, win):
 def test_segment_seams_inside_the_raster(nz, gpu_device, monkeypatch, seg, win):
     """SMRF_RING_SEG forces segments of 8 and 24 rows: 19 and 7 of them down the 150 rows, each starting 2R + 1 rows early"""
     switch(monkeypatch, "SMRF_RING_SEG", seg)
-    check(rough((150, 513), 963), ("shape", 150, 513), win, gpu_device, monkeypatch, folds_last=win in TAKEN[:2])
+    check(cross_raster((150, 513)), "cross_150x513", win, gpu_device, monkeypatch, folds_last=win in TAKEN[:2])
 
 
-@pytest.mark.parametrize("kind", ["inf", "inf_block", "constant", "four_levels", "subnormal", "near_max", "negative_zero"])
+@pytest.mark.parametrize("kind", VALUE_KINDS)
 def test_value_classes(nz, gpu_device, monkeypatch, kind):
     Zh = value_raster(kind)
     for win in VALUE_LISTS:
-        check(Zh, ("value", kind), win, gpu_device, monkeypatch, folds_last=len(win) == 2)
+        check(Zh, "value_" + kind, win, gpu_device, monkeypatch, folds_last=len(win) == 2)
 
 
 def test_the_table_is_the_default_and_keeps_the_last_window(nz, gpu_device, monkeypatch):
@@ -91,10 +71,10 @@ def test_the_table_is_the_default_and_keeps_the_last_window(nz, gpu_device, monk
     of dil_cross_adopt.inc fold and the results are the reference's"""
     import torch
     switch(monkeypatch, "SMRF_DIL_CROSS", None)
-    Zh = rough((97, 257), 654)
+    Zh = table_raster()
     Zd = torch.from_numpy(Zh).to(gpu_device)
     for win in TABLE_LISTS:
-        rm, rw, er, op = reference(("table",), Zh, win)
+        rm, rw, er, op = reference("cross_table", Zh, win)
         m, w, planes, route, taken = run_pf(Zd, win)
         assert same(m, rm) and same(w, rw), win
         assert holds(planes, er[-1]) and holds(planes, op[-1]), win
@@ -106,10 +86,10 @@ def test_the_workspace_plane_by_plane(nz, gpu_device, monkeypatch, win):
     (pf_host.restated) and the driver's plane rotation restated (pf_host.parent_steps) say which surface EACH of the three planes
     holds after the call; each is the reference's, bit for bit.  SMRF_DIL_CROSS 0 / 1 / 2 x SMRF_ERO_INC 0 / 2."""
     import torch
-    Zh = rough((97, 257), 654)
+    Zh = table_raster()
     Zd = torch.from_numpy(Zh).to(gpu_device)
-    rm, rw, er, op = reference(("table",), Zh, win)
-    surfaces = {"e": [torch.from_numpy(a).to(gpu_device) for a in er], "o": [torch.from_numpy(a).to(gpu_device) for a in op]}
+    rm, rw, er, op = reference("cross_table", Zh, win)
+    surfaces = {"e": er, "o": op}                           # (the windows before the last two: None, and never what a plane holds)
     for cross in (0, 1, 2):
         for inc_mode in (0, 2):
             switch(monkeypatch, "SMRF_DIL_CROSS", cross)
@@ -120,7 +100,8 @@ def test_the_workspace_plane_by_plane(nz, gpu_device, monkeypatch, win):
             assert sum(lab != "junk" for lab in labels) == (3 if len(win) > 1 else 2), (cross, inc_mode, win, labels)
             for k, lab in enumerate(labels):
                 if lab != "junk":
-                    assert torch.equal(planes[k], surfaces[lab[0]][lab[1]]), (cross, inc_mode, win, k, labels)
+                    want = torch.from_numpy(surfaces[lab[0]][lab[1]]).to(gpu_device)
+                    assert torch.equal(planes[k], want), (cross, inc_mode, win, k, labels)
             assert same(m, rm) and same(w, rw), (cross, inc_mode, win)
 
 

@@ -1,19 +1,19 @@
-"""The incremental erosion (csrc/morph_incero.h) and the large-disk ring kernels beside it at the shapes, values and
-launch grids where such kernels go wrong, against an INDEPENDENT reference (tests/morph_numpy.py, pinned to SciPy and the
-goldens by tests/test_morph_numpy.py): per radius the eroded and opened surfaces, mask and when_dropped, bit for bit.
-Radii beyond 4 min(rows, cols) are in scope: the reference is the period-2n reflect the kernels claim.
-SMRF_ERO_INC=2 unless said otherwise.  No raster mixes -0.0 with +0.0; NaN rasters never take the route (test_eligibility)."""
+"""The incremental erosion route of progressive_filter (csrc/morph_incero.h) and the large-disk ring
+kernels beside it on the GPU, at the shapes, values, launch grids and window lists where such kernels go wrong
+(tests/window_cases.py), against an INDEPENDENT reference (tests/morph_numpy.py, pinned to SciPy and the goldens by
+tests/test_morph_numpy.py): per radius the eroded and opened surfaces in the workspace, mask and when_dropped, bit for bit
+(tests/pf_run.py).  Radii beyond 4 min(rows, cols) are in scope: the reference is the period-2n reflect the kernels claim
+(DESIGN.md 2).  Then every radius against the ring erosion it replaces (SMRF_ERO_INC=2 against 0), and which windows are
+eligible.  The premises these tests rest on are held without a GPU by tests/test_window_cases_host.py."""
 import numpy as np
 import pytest
 
 import morph_numpy as mn
+import window_cases as wc
 from conftest import switch
-from pf_run import inc_rule, run_pf
+from pf_run import adopted_radii, check_pairs, holds, inc_rule, reference, rotation_plan, run_pf, same
 
 pytestmark = pytest.mark.gpu
-
-RADII = list(range(16, 65))
-W15_64 = list(range(15, 65))
 
 
 @pytest.fixture(scope="module")
@@ -23,196 +23,76 @@ def nz(gpu_device):
     return neilpy_amd
 
 
-def rough(shape, seed):
-    """finite, positive, rough at every scale, with isolated objects"""
-    rng = np.random.default_rng(seed)
-    Z = rng.normal(0, 1, shape).cumsum(0).cumsum(1) * .05 + 200 + rng.random(shape) * 2
-    return (Z + (rng.random(shape) < .05) * rng.uniform(1, 25, shape)).astype(np.float32)
+# ---- a. every radius in isolation: one table, one run.  The rows of the shapes and of the value classes keep the test names
+# and ids they have always had; every other row, and every new one, is a case of test_every_radius_alone ----
+def alone_rows(prefix):
+    return [pytest.param(c, id=c.id[len(prefix):]) for c in wc.ALONE if c.id.startswith(prefix)]
 
 
-def holds(planes, want):
-    import torch
-    w = torch.from_numpy(want).to(planes.device)
-    return any(torch.equal(planes[k], w) for k in range(3))
-
-
-def same(t, a):
-    return np.array_equal(t.cpu().numpy().astype(a.dtype), a)
-
-
-def check_pairs(Zh, gpu_device):
-    """every R in 16..64 alone: windows [R-1, R], the second one incremental; e_R, opened_R and opened_{R-1} in the
-    workspace's three planes, mask and when_dropped - all against the reference.  Returns the failing (R, what)."""
-    import torch
-    Zd = torch.from_numpy(Zh).to(gpu_device)
-    bad = []
-    for r in RADII:
-        m, w, planes, route, taken = run_pf(Zd, [r - 1, r])
-        assert taken == [0, 1], (r, taken, route)
-        rm, rw, er, op = mn.progressive_filter(Zh, [r - 1, r], 1, .15, return_when_dropped=True, return_surfaces=True)
-        for what, ok in (("e_R", holds(planes, er[1])), ("opened_R", holds(planes, op[1])), ("opened_R-1", holds(planes, op[0])),
-                         ("mask", same(m, rm)), ("when", same(w, rw))):
-            if not ok:
-                bad.append((r, what))
-    return bad
-
-
-# ---- a. every radius in isolation, awkward shapes -------------------------------------------------------------------
-SHAPES = [(151, 300),                                     # odd, not a multiple of 8
-          (1, 300), (3, 257), (7, 520),                   # fewer than 8 rows: one batch, DELTA rows early, rows folded many times
-          (90, 5), (33, 1), (64, 2),                      # narrower than the reach: the column fold wraps several periods
-          (24, 255), (24, 256), (24, 257)]                # strip edges
-
-
-@pytest.mark.parametrize("shape", SHAPES, ids=["%dx%d" % s for s in SHAPES])
-def test_every_radius_alone_against_the_reference(nz, gpu_device, monkeypatch, shape):
+def run_alone(case, gpu_device, monkeypatch):
     switch(monkeypatch, "SMRF_ERO_INC", "2")
-    bad = check_pairs(rough(shape, 100 + shape[0] + shape[1]), gpu_device)
+    for name, value in case.switches.items():
+        switch(monkeypatch, name, value)
+    bad = check_pairs(case.make(), gpu_device, wc.RADII, restated=case.restated)
     assert not bad, bad
 
 
-# ---- b. many strips, several segments: the three placement branches ------------------------------------------------
-def incero_grid(rows, cols, seg):
-    """inc_erode_launch's grid under a forced SMRF_RING_SEG: seg rounded up to a multiple of 8"""
-    seg = (seg + 7) // 8 * 8
-    return (cols + 255) // 256, (rows + seg - 1) // seg
+@pytest.mark.parametrize("case", alone_rows("shape_"))
+def test_every_radius_alone_against_the_reference(nz, gpu_device, monkeypatch, case):
+    run_alone(case, gpu_device, monkeypatch)
 
 
-GRIDS = [  # rows, cols, SMRF_RING_SEG, grid, remap branch
-    (40, 2048, 16, (8, 3), "mult8"),
-    (48, 4096, 20, (16, 2), "mult8"),                     # 20 -> 24
-    (40, 2100, 16, (9, 3), "ragged"),                     # 27 workgroups
-    (56, 4200, 20, (17, 3), "ragged"),                    # 20 -> 24: segments of 24, 24, 8 rows; 51 workgroups
-]
-_ref_cache = {}
+@pytest.mark.parametrize("case", alone_rows("value_"))
+def test_every_radius_alone_awkward_values(nz, gpu_device, monkeypatch, case):
+    run_alone(case, gpu_device, monkeypatch)
 
 
-def reference_15_64(key, Zh):
-    if key not in _ref_cache:
-        m, w, er, op = mn.progressive_filter(Zh, W15_64, 1, .15, return_when_dropped=True, return_surfaces=True)
-        _ref_cache[key] = (m, w, er[-1], op[-1])
-    return _ref_cache[key]
+@pytest.mark.parametrize("case", [pytest.param(c, id=c.id) for c in wc.ALONE if not c.id.startswith(("shape_", "value_"))])
+def test_every_radius_alone(nz, gpu_device, monkeypatch, case):
+    run_alone(case, gpu_device, monkeypatch)
 
 
-def check_15_64(Zh, key, gpu_device):
+# ---- b. windows 15..64 in one call: many strips, several segments, streaming stores ------------------------------------
+def check_15_64(Zh, case, gpu_device):
     import torch
-    m, w, planes, route, taken = run_pf(torch.from_numpy(Zh).to(gpu_device), W15_64)
+    m, w, planes, route, taken = run_pf(torch.from_numpy(Zh).to(gpu_device), wc.W15_64)
     assert taken == [0] + [1] * 49, taken
-    rm, rw, e_last, o_last = reference_15_64(key, Zh)
+    rm, rw, er, op = reference(case, Zh, wc.W15_64)
     assert same(m, rm) and same(w, rw)
-    assert holds(planes, e_last), "eroded surface of window 64"
-    assert holds(planes, o_last), "opened surface of window 64"
+    assert holds(planes, er[-1]), "eroded surface of window 64"
+    assert holds(planes, op[-1]), "opened surface of window 64"
 
 
 @pytest.mark.parametrize("remap", [None, "0"], ids=["xcd", "plain"])
-@pytest.mark.parametrize("rows,cols,seg,grid,branch", GRIDS, ids=["%dx%d" % (g[0], g[1]) for g in GRIDS])
+@pytest.mark.parametrize("rows,cols,seg,grid,branch", wc.GRIDS, ids=["%dx%d" % (g[0], g[1]) for g in wc.GRIDS])
 def test_many_strips_and_segments(nz, gpu_device, monkeypatch, rows, cols, seg, grid, branch, remap):
-    gx, gy = incero_grid(rows, cols, seg)
-    assert (gx, gy) == grid and gy > 1
-    if branch == "mult8":
-        assert gx % 8 == 0
-    else:
-        assert gx > 8 and gx % 8 != 0 and (gx * gy) % 8 != 0
+    wc.assert_grid(rows, cols, seg, grid, branch)
     switch(monkeypatch, "SMRF_ERO_INC", "2")
     switch(monkeypatch, "SMRF_RING_SEG", seg)
     switch(monkeypatch, "SMRF_XCD_REMAP", remap)
-    check_15_64(rough((rows, cols), 7 + cols), ("grid", rows, cols), gpu_device)
+    check_15_64(wc.grid_raster(rows, cols), "grid_%dx%d" % (rows, cols), gpu_device)
 
 
-# ---- c. values ------------------------------------------------------------------------------------------------------
-def value_raster(kind):
-    shape = (151, 300)
-    rng = np.random.default_rng(31)
-    Z = rough(shape, 32)
-    if kind == "inf":
-        Z[rng.random(shape) < .01] = np.inf
-        Z[rng.random(shape) < .01] = -np.inf
-    elif kind == "inf_block":                             # whole disks of +inf: the erosion's own identity element as a VALUE
-        Z[:, :150] = np.inf
-        Z[100:, :] = np.inf
-    elif kind == "constant":
-        Z[...] = np.float32(123.456)
-    elif kind == "four_levels":
-        Z = np.floor(rng.random(shape) * 4).astype(np.float32) * np.float32(2.5) + 1
-    elif kind == "subnormal":
-        Z = (rng.integers(1, 1 << 22, shape) * np.float32(1e-45)).astype(np.float32)
-        assert (Z > 0).all() and (Z < np.finfo(np.float32).tiny).all()
-    elif kind == "near_max":
-        Z = rng.uniform(-3e38, 3e38, shape).astype(np.float32)
-    elif kind == "negative_zero":
-        Z = -np.abs(Z - 205)
-        Z[rng.random(shape) < .1] = -0.0
-        assert np.signbit(Z).all() and (Z == 0).any()
-    return Z
-
-
-@pytest.mark.parametrize("kind", ["inf", "inf_block", "constant", "four_levels", "subnormal", "near_max", "negative_zero"])
-def test_every_radius_alone_awkward_values(nz, gpu_device, monkeypatch, kind):
-    switch(monkeypatch, "SMRF_ERO_INC", "2")
-    bad = check_pairs(value_raster(kind), gpu_device)
-    assert not bad, bad
-
-
-# ---- d. streaming stores and forced segment lengths -----------------------------------------------------------------
-@pytest.mark.parametrize("name,value", [("SMRF_NT", "1"), ("SMRF_RING_SEG", "8"), ("SMRF_RING_SEG", "50"), ("SMRF_RING_SEG", "136")])
-@pytest.mark.parametrize("shape", [(1100, 520), (151, 300)], ids=["1100x520", "151x300"])
+@pytest.mark.parametrize("name,value", wc.SEGMENT_SWITCHES)
+@pytest.mark.parametrize("shape", wc.SEGMENT_SHAPES, ids=["%dx%d" % s for s in wc.SEGMENT_SHAPES])
 def test_stores_and_segments(nz, gpu_device, monkeypatch, shape, name, value):
     switch(monkeypatch, "SMRF_ERO_INC", "2")
     switch(monkeypatch, name, value)
-    check_15_64(rough(shape, 55), ("seg",) + shape, gpu_device)
+    check_15_64(wc.segment_raster(shape), "segments_%dx%d" % shape, gpu_device)
 
 
-# ---- e. plane rotation ----------------------------------------------------------------------------------------------
-JOINS = ["repeat", "descent", "chain", "fused", "zero", "r65", "r70"]
-
-
-def window_list(k):
-    """three consecutive runs inside 15..64 joined by two of JOINS (every kind comes up 8-9 times over the 30 lists)"""
-    rng = np.random.default_rng(9000 + k)
-    out = []
-    for j in range(3):
-        n = int(rng.integers(2, 6))
-        a = int(rng.integers(15, 65 - n + 1))
-        run = list(range(a, a + n))
-        out += run
-        if j == 2:
-            break
-        kind = JOINS[(2 * k + j) % len(JOINS)]
-        if kind == "repeat":
-            out += [run[-1]]
-        elif kind == "descent":
-            out += [run[-1] - int(rng.integers(1, 4))]
-        elif kind == "chain":
-            out += [1, 2, 3]
-        elif kind == "fused":
-            out += [int(rng.choice([5, 8]))]
-        elif kind == "zero":
-            out += [0]
-        else:
-            out += [65 if kind == "r65" else 70]
-    return out
-
-
-LISTS = [window_list(k) for k in range(30)]
-_rot_cache = {}
-
-
+# ---- c. plane rotation -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("fused", [None, "0", "2"], ids=["fused_default", "fused0", "fused2"])
 @pytest.mark.parametrize("k", range(30))
 def test_plane_rotation_across_routes(nz, gpu_device, monkeypatch, k, fused):
     import torch
     from neilpy_amd import _lib
-    win = LISTS[k]
-    # the premise: under mode 2 some window takes the route and a later one leaves it (judged on the radii alone: every
-    # radius 15..64 runs as two ring passes on a raster this small, asserted below)
-    two_pass = [int(15 <= r <= 64) for r in win]
-    plan = inc_rule(win, [_lib.ROUTE_TWO_PASS if t else _lib.ROUTE_DIRECT for t in two_pass], 2)
+    win = wc.LISTS[k]
+    # the premise: under mode 2 some window takes the route and a later one leaves it
+    plan = rotation_plan(win)
     assert any(plan[i] and not plan[i + 1] for i in range(len(win) - 1)), win
-    Zh = rough((120, 400), 77)
-    if k not in _rot_cache:
-        m, w, _, op = mn.progressive_filter(Zh, win, 1, .15, return_when_dropped=True, return_surfaces=True)
-        _rot_cache[k] = (m, w, op[-1])
-    rm, rw, o_last = _rot_cache[k]
+    Zh = wc.rotation_raster()
+    rm, rw, _, op = reference("rotation", Zh, win)
     Zd = torch.from_numpy(Zh).to(gpu_device)
     switch(monkeypatch, "SMRF_FUSED", fused)
     for mode in (0, 1, 2):
@@ -231,17 +111,116 @@ def test_plane_rotation_across_routes(nz, gpu_device, monkeypatch, k, fused):
         if mode == 2:
             assert taken == plan
         assert same(m, rm) and same(w, rw), (mode, win)
-        assert holds(planes, o_last), (mode, win)
+        assert holds(planes, op[-1]), (mode, win)
 
 
 def test_public_entry_point_numpy_and_tensor(nz, gpu_device, monkeypatch):
     import torch
     switch(monkeypatch, "SMRF_ERO_INC", "2")
-    win = np.array(LISTS[3])
-    Zh = rough((120, 400), 78)
+    win = np.array(wc.LISTS[3])
+    Zh = wc.rough((120, 400), 78)
     rm, rw = mn.progressive_filter(Zh, win, 1, .15, return_when_dropped=True)
     m, w = nz.progressive_filter(Zh, win, 1, .15, return_when_dropped=True)
     assert isinstance(m, np.ndarray) and np.array_equal(m, rm) and np.array_equal(w, rw)
     mt, wt = nz.progressive_filter(torch.from_numpy(Zh).to(gpu_device), win, 1, .15, return_when_dropped=True)
     assert isinstance(mt, torch.Tensor) and mt.is_cuda
     assert np.array_equal(mt.cpu().numpy().astype(bool), rm) and np.array_equal(wt.cpu().numpy(), rw)
+
+
+@pytest.mark.parametrize("lo,hi", [(15, 40), (30, 50)])
+def test_whole_calls(nz, gpu_device, monkeypatch, lo, hi):
+    """windows 15..40 and 30..50 on three strips give the reference's mask and when_dropped"""
+    import torch
+    switch(monkeypatch, "SMRF_ERO_INC", "2")
+    Z = wc.random_raster((150, 600), 33)
+    windows = list(range(lo, hi + 1))
+    m, w, planes, route, taken = run_pf(torch.from_numpy(Z).to(gpu_device), windows)
+    assert taken == [0] + [1] * (len(windows) - 1), (taken, route)
+    rm, rw = mn.progressive_filter(Z, windows, 1, .15, return_when_dropped=True)
+    assert same(m, rm) and same(w, rw)
+
+
+# ---- d. against the ring erosion it replaces, and eligibility -----------------------------------------------------------
+@pytest.mark.parametrize("rows,cols,seg", [(150, 600, None), (1100, 520, None), (1100, 520, "136"), (40, 300, None)])
+def test_every_radius_equals_the_ring_erosion(nz, gpu_device, monkeypatch, rows, cols, seg):
+    """windows 1..64: a raster smaller than the large disks (150 x 600), one cut into several row segments per strip with a
+    ragged last strip and last segment (1100 x 520; also with forced 136-row segments: warm-up rows of one segment inside
+    another's outputs), and one shorter than most disks (40 rows: rows reflected several times over)"""
+    import torch
+    from neilpy_amd import _lib
+    switch(monkeypatch, "SMRF_RING_SEG", seg)
+    Zh = wc.synth_raster(rows, cols, 11)
+    Zd = torch.from_numpy(Zh).to(gpu_device)
+    win = np.arange(1, 65)
+    switch(monkeypatch, "SMRF_ERO_INC", "0")
+    m0, w0, p0, r0, t0 = run_pf(Zd, win)
+    assert t0 == [0] * 64
+    switch(monkeypatch, "SMRF_ERO_INC", "2")
+    m2, w2, p2, r2, t2 = run_pf(Zd, win)
+    assert r2 == r0                                           # still two passes
+    first_two_pass = r0.index(_lib.ROUTE_TWO_PASS)
+    want = [int(i > first_two_pass and r0[i] == _lib.ROUTE_TWO_PASS and r0[i - 1] == _lib.ROUTE_TWO_PASS and win[i] >= 16)
+            for i in range(64)]
+    assert t2 == want and sum(t2) >= 49
+    assert torch.equal(m0, m2) and torch.equal(w0, w2)
+    # the last opened surface and the last eroded surface are in the workspace, in planes whose roles rotate
+    last = torch.from_numpy(Zh).to(gpu_device)
+    for r in win:
+        e = nz.erosion(last, radius=int(r))
+        last = nz.dilation(e, radius=int(r))
+    for p in (p0, p2):
+        assert any(torch.equal(p[k], last) for k in range(3))
+        assert any(torch.equal(p[k], e) for k in range(3))
+
+
+def test_eligibility(nz, gpu_device, monkeypatch):
+    """the incremental erosion is taken for a two-pass window whose radius is the previous window's + 1 and whose previous
+    window ran as two ring passes - not after a gap, not for the first two-pass window, not on a raster with NaNs, not with
+    impl = direct, not in fp64, and with SMRF_ERO_INC=1 only where the table adopts the radius; the same bits every time"""
+    import torch
+    from neilpy_amd import _lib
+    Zh = wc.synth_raster(300, 700, 5)
+    Zd = torch.from_numpy(Zh).to(gpu_device)
+    win = [15, 16, 18, 19, 30, 31, 31, 32, 20, 21]
+    switch(monkeypatch, "SMRF_ERO_INC", "0")
+    m0, w0, _, r0, t0 = run_pf(Zd, win)
+    assert t0 == [0] * len(win) and r0 == [_lib.ROUTE_TWO_PASS] * len(win)
+    switch(monkeypatch, "SMRF_ERO_INC", "2")
+    m2, w2, _, r2, t2 = run_pf(Zd, win)
+    assert r2 == r0
+    assert t2 == [0, 1, 0, 1, 0, 1, 0, 1, 0, 1]
+    assert torch.equal(m0, m2) and torch.equal(w0, w2)
+    # a fused window in between: 14 runs as one launch under SMRF_FUSED=2, so 15 has no eroded plane to start from
+    switch(monkeypatch, "SMRF_FUSED", "2")
+    _, _, _, rf, tf = run_pf(Zd, [13, 14, 15, 16])
+    assert rf[1] == _lib.ROUTE_FUSED and rf[2:] == [_lib.ROUTE_TWO_PASS] * 2 and tf == [0, 0, 0, 1]
+    switch(monkeypatch, "SMRF_FUSED", None)
+    # impl = direct: the footprint-gather kernels, never
+    md, wd, _, rd, td = run_pf(Zd, [15, 16, 17], impl=_lib.IMPL_DIRECT)
+    assert rd == [_lib.ROUTE_DIRECT] * 3 and td == [0, 0, 0]
+    mr, wr, _, rr, tr = run_pf(Zd, [15, 16, 17], impl=_lib.IMPL_RING)
+    assert tr == [0, 1, 1] and torch.equal(md, mr) and torch.equal(wd, wr)
+    # NaNs: scipy's NaN rule stays on the ring kernels (found by the library's own scan, or told by the caller)
+    Zn = Zh.copy()
+    Zn[17, 33] = np.nan
+    Zn[200:203, 650:] = np.nan
+    Znd = torch.from_numpy(Zn).to(gpu_device)
+    mn_, wn, _, _, tn = run_pf(Znd, np.arange(1, 41))
+    assert tn == [0] * 40
+    switch(monkeypatch, "SMRF_ERO_INC", "0")
+    mn0, wn0, _, _, _ = run_pf(Znd, np.arange(1, 41))
+    assert torch.equal(mn_, mn0) and torch.equal(wn, wn0)
+    switch(monkeypatch, "SMRF_ERO_INC", "2")
+    _, _, _, _, tn1 = run_pf(Znd, [15, 16, 17], nan_aware=1)
+    assert tn1 == [0, 0, 0]
+    # fp64 keeps the ring erosion
+    _, _, _, r64, t64 = run_pf(Zd.double(), [15, 16, 17])
+    assert r64 == [_lib.ROUTE_TWO_PASS] * 3 and t64 == [0, 0, 0]
+    # the default (SMRF_ERO_INC unset = 1): the per-radius table of csrc/ero_inc_adopt.inc
+    switch(monkeypatch, "SMRF_ERO_INC", None)
+    adopt = adopted_radii()
+    m1, w1, _, r1, t1 = run_pf(Zd, np.arange(1, 65))
+    assert t1 == [int(r >= 16 and adopt[r]) for r in range(1, 65)]
+    switch(monkeypatch, "SMRF_ERO_INC", "0")
+    m00, w00, _, _, _ = run_pf(Zd, np.arange(1, 65))
+    assert torch.equal(m1, m00) and torch.equal(w1, w00)

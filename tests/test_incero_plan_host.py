@@ -199,6 +199,43 @@ def test_the_restated_planner_reads_what_the_compiled_kernels_read():
             assert got <= NP * TAB[r][0]                   # never more reads than one pair per job
 
 
+# ---- the plain plan of a batch (job order and first-update table), restated on its own from ero_inc.inc and the header's
+# batch geometry: cross loads before the prefetch, stores one batch late, the ring turned by an untied first update per slot ----
+def batch_plan(n, reach, pairs):
+    """jobs (row pair p, cell pair k) by ascending slot 2p - dy + reach; first[s] = position of the first job updating slot s"""
+    nacc = 2 * reach + ROWS
+    slot = [2 * (j // n) - pairs[j % n][0] + reach for j in range(NP * n)]
+    seq = [j for s in range(nacc) for j in range(NP * n) if slot[j] == s]
+    first = {}
+    for i, j in enumerate(seq):
+        for h in (0, 1):
+            first.setdefault(slot[j] + h, i)
+    return nacc, slot, seq, first
+
+
+def test_first_update_table_names_every_touched_slot_once():
+    for r in RADII:
+        n, reach, pairs = TAB[r]
+        if n == 0:
+            continue
+        assert max(max(abs(dy), dx) for dy, dx in pairs) == reach
+        nacc, slot, seq, first = batch_plan(n, reach, pairs)
+        assert sorted(seq) == list(range(NP * n)), r                      # every job once
+        touched = {}
+        for i, j in enumerate(seq):
+            for h in (0, 1):
+                s = slot[j] + h
+                assert 0 <= s < nacc, (r, s)
+                touched.setdefault(s, []).append(i)
+        assert set(first) == set(touched), r
+        for s, where in touched.items():
+            assert sum(i == first[s] for i in where) == 1, (r, s)         # exactly one first update
+            assert first[s] == min(where), (r, s)
+            # the value slot s continues is still there: slot s + 8 has its own first update later
+            if s + ROWS in first:
+                assert first[s] < first[s + ROWS], (r, s)
+
+
 def test_mirror_plans_halve_the_reads_where_nothing_blocks():
     """8-cell rims (two mirror pairs far apart in dy) need no fallback: 8 pairs of reads for 16 jobs"""
     for r in (18, 23, 28, 31, 41, 46):

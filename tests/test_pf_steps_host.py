@@ -7,8 +7,7 @@ import pytest
 
 import pf_host
 from pf_host import CHAIN, CROSS, DILATE, DILATE_CROSS, ERODE, FUSED_OPEN, INC_ERODE, NO_PLANE, PATTERNS, PLANE_Z, Step, TWO_PASS
-from test_gpu_dil_cross import WINDOW_LISTS as DIL_CROSS_LISTS
-from test_gpu_incero_edges import LISTS as ROTATION_LISTS
+from window_cases import LISTS as ROTATION_LISTS, WINDOW_LISTS as DIL_CROSS_LISTS
 
 
 @pytest.fixture(scope="module")
