@@ -574,6 +574,13 @@ SMRF_API int smrf_points_nn_sum_f64(const double* d_x, int64_t n, double* d_sum,
                      size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * point-set matching: assignment and bidimensional regression (neilpy_amd/matching.py)
+ * ------------------------------------------------------------------------------------------ */
+/* The smrf_assign_* entry points have a header of their own, which is part of this one: same status codes, same
+ * conventions (sizing call that returns 0 out of range, argument checks before any launch, `void* stream` last). */
+#include "smrf_assign.h"
+
+/* ------------------------------------------------------------------------------------------
  * point cloud -> boolean voxel model (neilpy_amd/voxel.py)
  * ------------------------------------------------------------------------------------------ */
 /* The cloud is three contiguous coordinate arrays of one dtype, 1 <= npoints <= 2^31 - 1.  The volume has nx x ny x nz

@@ -33,7 +33,7 @@ def hipcc():
 
 def units():
     """(object name, source, extra flags)"""
-    out = [(n + ".o", os.path.join(CSRC, n + ".hip"), []) for n in ("core", "morph", "incero", "chain", "grid", "springs", "fda", "tail", "spline", "terrain", "surface", "nearest", "focal", "morphometry", "points", "voxel", "relief")]
+    out = [(n + ".o", os.path.join(CSRC, n + ".hip"), []) for n in ("core", "morph", "incero", "chain", "grid", "springs", "fda", "tail", "spline", "terrain", "surface", "nearest", "focal", "morphometry", "points", "voxel", "relief", "assign")]
     for f64 in (0, 1):
         for p in range(RING_PARTS):
             out.append(("ring_%s_p%d.o" % ("f64" if f64 else "f32", p), os.path.join(CSRC, "ring_part.hip"),
@@ -42,7 +42,8 @@ def units():
 
 
 def newest_header():
-    t = os.path.getmtime(os.path.join(ROOT, "include", "smrf_hip.h"))
+    inc = os.path.join(ROOT, "include")
+    t = max(os.path.getmtime(os.path.join(inc, f)) for f in os.listdir(inc) if f.endswith(".h"))
     for f in os.listdir(CSRC):
         if f.endswith((".h", ".inc")):
             t = max(t, os.path.getmtime(os.path.join(CSRC, f)))
