@@ -41,6 +41,9 @@
  *   smrf_morphometry_*, smrf_vip_*, smrf_ashift_*
  *                             scaled_morphometry(), vip_score() and ashift(), neilpy/neilpy.py:2472, :1832, :1290
  *                             (host side: neilpy_amd/morphometry.py)
+ *   smrf_footprint_*          scipy.ndimage.grey_erosion / grey_dilation with any flat footprint, modes 'reflect' and
+ *                             'nearest', and the openings, closings, top-hats and gradient composed of them (host
+ *                             side: neilpy_amd/morphology.py)
  *
  * Conventions
  *   - every pointer named d_* is DEVICE memory (hipMalloc or a torch CUDA tensor's data_ptr);
@@ -515,6 +518,13 @@ SMRF_API int smrf_focal_mix_f32(const float* d_Z, const float* d_M, const double
                    double blend_rate, double* d_out, int64_t n, void* stream);
 SMRF_API int smrf_focal_mix_f64(const double* d_Z, const double* d_M, const double* d_STD, const double* d_lohi,
                    double blend_rate, double* d_out, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * grey morphology with arbitrary flat footprints (neilpy_amd/morphology.py)
+ * ------------------------------------------------------------------------------------------ */
+/* The smrf_footprint_* entry points have a header of their own, which is part of this one: same status codes, same
+ * conventions (argument checks before any launch, `void* stream` last). */
+#include "smrf_footprint.h"
 
 /* ------------------------------------------------------------------------------------------
  * strided stencils: scaled_morphometry, vip_score, ashift (neilpy_amd/morphometry.py)
