@@ -520,11 +520,48 @@ SMRF_API int smrf_focal_mix_f64(const double* d_Z, const double* d_M, const doub
                    double blend_rate, double* d_out, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * grey morphology with arbitrary flat footprints (neilpy_amd/morphology.py)
+ * grey morphology with arbitrary flat footprints: scipy.ndimage.grey_erosion / grey_dilation and what rests on them
+ * (neilpy_amd/morphology.py)
  * ------------------------------------------------------------------------------------------ */
-/* The smrf_footprint_* entry points have a header of their own, which is part of this one: same status codes, same
- * conventions (argument checks before any launch, `void* stream` last). */
-#include "smrf_footprint.h"
+#define SMRF_FOOTPRINT_REFLECT 0  /* border mode 'reflect': the period-2n fold (d c b a | a b c d | d c b a) */
+#define SMRF_FOOTPRINT_NEAREST 1  /* border mode 'nearest': indices clamped to the raster */
+#define SMRF_FOOTPRINT_IMPL_AUTO 0 /* RUNS when its LDS planes fit SMRF_FOOTPRINT_TILE_BYTES and the footprint has at
+                                      least SMRF_FOOTPRINT_RUNS_MIN_TAPS members, TAPS otherwise */
+#define SMRF_FOOTPRINT_IMPL_RUNS 1 /* tile + halo in LDS, power-of-two min / max planes, two LDS reads per run of
+                                      consecutive members; SMRF_E_UNSUPPORTED when the planes do not fit */
+#define SMRF_FOOTPRINT_IMPL_TAPS 2 /* one compare per member, every sample from global memory; any footprint, any
+                                      raster; same values as RUNS */
+#define SMRF_FOOTPRINT_TILE_BYTES 53248 /* LDS of one workgroup's planes: SMRF_FOCAL_TILE_BYTES, three workgroups per CU */
+#define SMRF_FOOTPRINT_RUNS_MIN_TAPS 9
+#define SMRF_FOOTPRINT_STORE 0      /* d_out = the filter's result */
+#define SMRF_FOOTPRINT_SUB_MINUS 1  /* d_out = d_sub - result (white top-hat's second launch) */
+#define SMRF_FOOTPRINT_MINUS_SUB 2  /* d_out = result - d_sub (black top-hat's second launch) */
+#define SMRF_FOOTPRINT_GRADIENT 3   /* d_out = max - min over the same samples (is_dilate is not looked at): the
+                                       morphological gradient of a footprint that is its own mirror image */
+
+/* The LDS a workgroup of the RUNS path may take, SMRF_FOOTPRINT_TILE_BYTES. */
+SMRF_API int smrf_footprint_tile_bytes(void);
+/* The path a launch with this plan head takes: 0 = TAPS, 1 = RUNS, or a negative SMRF_E_* code where the launch would be
+ * refused (a malformed head, RUNS forced on planes that do not fit).  Host logic only. */
+SMRF_API int smrf_footprint_path(const int* h_head, int elem_size, int epilogue, int impl);
+/* One launch over a contiguous rows x cols raster.  The plan comes from the host (neilpy_amd.morphology.plan):
+ *   h_head (host, 24 int32): ntaps, nruns, r_lo, c_lo, bh, bw, maxlevel, nplanes, slot[16] - the members' count, the
+ *     count of their runs, the least (drow, dcol) of a member and the rows and columns of the members' bounding box, the
+ *     largest floor(log2(run length)), and for every level up to it the LDS plane (0 .. nplanes - 1) that holds it;
+ *   d_plan (device, int32): ntaps records (drow, dcol), the first visited member first, then nruns records (trow, tcol,
+ *     tcol2, slot): a run of L members from (drow, dcol0) at level k = floor(log2 L) reads the plane in `slot` at tile
+ *     row drow - r_lo and tile columns dcol0 - c_lo and dcol0 - c_lo + L - 2^k.
+ * Offsets are the samples' own: the cell (r, c) reads X[idx(r + drow), idx(c + dcol)], idx the border mode's index rule,
+ * so a dilation's plan holds the footprint mirrored about its centre.  The result is the minimum (is_dilate 0) or
+ * maximum (1) of the samples, NaN iff the first visited sample is NaN (scipy.ndimage's rule); nan_aware 0 promises a
+ * raster without NaN and spares the RUNS path one read per cell.  d_sub is read by epilogues 1 and 2 only.  Every
+ * global index goes through idx, whatever the plan holds. */
+SMRF_API int smrf_footprint_filter_f32(const float* d_in, const float* d_sub, float* d_out, int rows, int cols,
+                   const void* d_plan, const int* h_head, int is_dilate, int mode, int nan_aware, int impl,
+                   int epilogue, void* stream);
+SMRF_API int smrf_footprint_filter_f64(const double* d_in, const double* d_sub, double* d_out, int rows, int cols,
+                   const void* d_plan, const int* h_head, int is_dilate, int mode, int nan_aware, int impl,
+                   int epilogue, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * strided stencils: scaled_morphometry, vip_score, ashift (neilpy_amd/morphometry.py)
@@ -586,9 +623,43 @@ SMRF_API int smrf_points_nn_sum_f64(const double* d_x, int64_t n, double* d_sum,
 /* ------------------------------------------------------------------------------------------
  * point-set matching: assignment and bidimensional regression (neilpy_amd/matching.py)
  * ------------------------------------------------------------------------------------------ */
-/* The smrf_assign_* entry points have a header of their own, which is part of this one: same status codes, same
- * conventions (sizing call that returns 0 out of range, argument checks before any launch, `void* stream` last). */
-#include "smrf_assign.h"
+/* Clouds are contiguous float64 (n, dim) arrays, dim 2 or 3, finite.  One problem is solved by one wave64 out of its
+ * slice of LDS: the coordinates, the row duals and, from column 256 on, the per-column state.  Without the cost matrix
+ * a problem of nr <= nc points takes 8 (dim + 1) nr + 4 nr + 8 dim nc + 28 max(0, nc - 256) bytes, and one workgroup may
+ * claim the 160 KiB of a gfx950 CU; smrf_assign_limit() is the largest n whose n x n problem of dimension 3 fits, 1943.
+ * Either side of a problem may be that long, no longer.
+ * smrf_assign_workspace_bytes(nrows, ncols, dim) bytes of device scratch (0 for arguments out of range) serve every call
+ * below: an int64 count of sample entries out of range, then an int32 status that the solve ORs into (1: a problem had
+ * no finite augmenting path, which takes an overflowed cost; 2: a sample entry out of range met in the launch).  The
+ * calls clear it first. */
+SMRF_API int smrf_assign_limit(void);
+SMRF_API size_t smrf_assign_workspace_bytes(int64_t nrows, int64_t ncols, int dim);
+/* How the library would run an nrows x ncols problem: h_route[0] = the number of columns whose state lives in registers
+ * (the columns from there on keep it in LDS), [1] = 1 when the cost matrix is kept in LDS, 0 when costs are recomputed
+ * from the coordinates, [2] = waves (problems) per workgroup of a large batch, [3] = LDS bytes per wave, [4] = the
+ * largest n whose n x n problem of this dimension keeps its costs in LDS. */
+SMRF_API int smrf_assign_route(int64_t nrows, int64_t ncols, int dim, int* h_route);
+/* hungarian_algorithm(): the minimum-cost assignment of d_xy (nrows, dim) to d_ab (ncols, dim) under the cost
+ * sqrt((x0-a0)*(x0-a0) + (x1-a1)*(x1-a1) [+ (x2-a2)*(x2-a2)]), every operation rounded.  min(nrows, ncols) entries each:
+ * d_row_ind ascending, d_col_ind, d_costs = the cost of each pair.  Shortest augmenting paths with float64 duals; among
+ * columns at the lowest tentative distance an unassigned one, among those the lowest index.  One launch of one wave. */
+SMRF_API int smrf_assign_solve_f64(const double* d_xy, int64_t nrows, const double* d_ab, int64_t ncols, int dim,
+                     int64_t* d_row_ind, int64_t* d_col_ind, double* d_costs, void* d_workspace,
+                     size_t workspace_bytes, void* stream);
+/* h_bad = the number of the k * n entries of d_samples outside 0 .. m - 1, in one reduction (an integer count).
+ * Synchronises the stream. */
+SMRF_API int smrf_assign_samples_check(const int64_t* d_samples, int64_t k, int64_t n, int64_t m, int64_t* h_bad,
+                     void* d_workspace, size_t workspace_bytes, void* stream);
+/* bdr() / bdr_bootstrap(): k bidimensional regressions of d_ab's points on d_xy (n, 2), n >= 3, in one launch.
+ * solve == 0: k = 1, m = n, no samples: row i of d_ab belongs to row i of d_xy (any n).  solve != 0: sample s is the rows
+ * d_samples[s][0 .. n) of d_ab (m, 2) (NULL: m = n, the rows in order); its wave solves the n x n assignment against
+ * d_xy as the call above does, n <= smrf_assign_limit(), and regresses the matched points.  Per sample: d_scalars[s][9] =
+ * beta1 beta2 alpha1 alpha2 rsquare D Dmax DI F, d_aprime[s][n], d_bprime[s][n], d_rsquare[s], d_di[s]; any may be NULL,
+ * not all of scalars, rsquare and DI.  float64 add, multiply, divide and square root, each rounded; a sum takes element
+ * l, l + 64, ... on lane l from +0.0, then p += p[lane ^ o] for o = 32 .. 1.  No float atomics. */
+SMRF_API int smrf_assign_bdr_f64(const double* d_xy, int64_t n, const double* d_ab, int64_t m, const int64_t* d_samples,
+                     int64_t k, int solve, double* d_scalars, double* d_aprime, double* d_bprime, double* d_rsquare,
+                     double* d_di, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * point cloud -> boolean voxel model (neilpy_amd/voxel.py)

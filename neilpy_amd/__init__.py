@@ -15,14 +15,14 @@ counting sort into a cell grid and a ring search (neilpy_amd/points.py).  ``voxe
 voxel model ``np.histogramdd`` and a threshold give, bit for bit: a scatter into a bit set and a byte expansion with the
 bottom fill (neilpy_amd/voxel.py).  ``colortable_shade`` / ``swiss_shading`` / ``brassel_atmospheric_perspective`` turn a DTM and its
 hillshade into the coloured relief image, over ``raster_stats`` (NaN-ignoring moments in a fixed summation order and an
-exact radix-select median), ``normalize`` and ``rmse`` (neilpy_amd/relief.py).  The module ``neilpy_amd.matching`` holds
-``hungarian_algorithm``, which matches two point sets at the least total distance, ``bdr``, the bidimensional regression,
-and ``bdr_bootstrap``, its bootstrap over matched samples: one wave64 per assignment problem, shortest augmenting paths
-out of LDS, every sample of the bootstrap solved and regressed in one launch.  The module ``neilpy_amd.morphology`` holds
-``grey_erosion`` / ``grey_dilation`` / ``grey_opening`` / ``grey_closing`` / ``white_tophat`` / ``black_tophat`` /
-``morphological_gradient``, ``scipy.ndimage``'s grey morphology for any flat footprint (``size=`` or ``footprint=``,
-modes 'reflect' and 'nearest') bit for bit, with the host helpers ``rectangle`` / ``square`` / ``diamond``: a tap kernel
-and an LDS kernel that takes each run of consecutive members from two reads of a power-of-two min / max plane.
+exact radix-select median), ``normalize`` and ``rmse`` (neilpy_amd/relief.py).  ``hungarian_algorithm`` matches two
+point sets at the least total distance, ``bdr`` is the bidimensional regression and ``bdr_bootstrap`` its bootstrap over
+matched samples: one wave64 per assignment problem, shortest augmenting paths out of LDS, every sample of the bootstrap
+solved and regressed in one launch (neilpy_amd/matching.py).  ``grey_erosion`` / ``grey_dilation`` / ``grey_opening`` /
+``grey_closing`` / ``white_tophat`` / ``black_tophat`` / ``morphological_gradient`` are ``scipy.ndimage``'s grey
+morphology for any flat footprint (``size=`` or ``footprint=``, modes 'reflect' and 'nearest') bit for bit, with the host
+helpers ``rectangle`` / ``square`` / ``diamond``: a tap kernel and an LDS kernel that takes each run of consecutive
+members from two reads of a power-of-two min / max plane (neilpy_amd/morphology.py).
 """
 from ._lib import SmrfHipError, load as load_library, LIB_PATH          # noqa: F401
 from .affine import Affine, edges_from_IT, from_origin, write_worldfile                 # noqa: F401
@@ -31,8 +31,9 @@ from .api import (create_dem, dilation, disk, erosion, inpaint_nans_by_fda, inpa
                   opening, progressive_filter, pssm, smrf)
 from .focal import distance_kernel, focal_convolve, reduce_peaks, std, topographic_position_index   # noqa: F401
 from .las import read_las, read_las_xyz, write_las                         # noqa: F401
-from . import matching                                                     # noqa: F401
-from . import morphology                                                   # noqa: F401
+from .matching import bdr, bdr_bootstrap, hungarian_algorithm              # noqa: F401
+from .morphology import (black_tophat, diamond, grey_closing, grey_dilation, grey_erosion, grey_opening,   # noqa: F401
+                         morphological_gradient, rectangle, square, white_tophat)
 from .morphometry import ashift, scaled_morphometry, triangle_height, vip_score   # noqa: F401
 from .nearest import inpaint_nearest, nearest_source                      # noqa: F401
 from .points import chamfer_distance, nearest_points                       # noqa: F401

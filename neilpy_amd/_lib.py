@@ -112,6 +112,10 @@ SIGNATURES = {
     "smrf_focal_minmax_f64": (_i, [_p, _i64, _p, _sz, _p]),
     "smrf_focal_mix_f32": (_i, [_p, _p, _p, _p, _d, _p, _i64, _p]),
     "smrf_focal_mix_f64": (_i, [_p, _p, _p, _p, _d, _p, _i64, _p]),
+    "smrf_footprint_tile_bytes": (_i, []),
+    "smrf_footprint_path": (_i, [_p, _i, _i, _i]),
+    "smrf_footprint_filter_f32": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "smrf_footprint_filter_f64": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _i, _p]),
     "smrf_morphometry_f32": (_i, [_p, _i, _i, _i, _d, _d, _d, _d, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "smrf_morphometry_f64": (_i, [_p, _i, _i, _i, _d, _d, _d, _d, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "smrf_vip_f32": (_i, [_p, _i, _i, _d, _d, _d, _d, _p, _p]),
@@ -123,6 +127,12 @@ SIGNATURES = {
     "smrf_points_nn_build_f64": (_i, [_p, _i64, _i, C.POINTER(_d), _p, _sz, _p]),
     "smrf_points_nn_search_f64": (_i, [_p, _i64, _p, _i64, _i, C.POINTER(_d), _p, _p, _p, _sz, _p]),
     "smrf_points_nn_sum_f64": (_i, [_p, _i64, _p, _p, _sz, _p]),
+    "smrf_assign_limit": (_i, []),
+    "smrf_assign_workspace_bytes": (_sz, [_i64, _i64, _i]),
+    "smrf_assign_route": (_i, [_i64, _i64, _i, C.POINTER(_i)]),
+    "smrf_assign_solve_f64": (_i, [_p, _i64, _p, _i64, _i, _p, _p, _p, _p, _sz, _p]),
+    "smrf_assign_samples_check": (_i, [_p, _i64, _i64, _i64, C.POINTER(_i64), _p, _sz, _p]),
+    "smrf_assign_bdr_f64": (_i, [_p, _i64, _p, _i64, _p, _i64, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "smrf_voxel_bounds_f32": (_i, [_p, _p, _p, _i64, C.POINTER(_d), C.POINTER(_i64), _p, _sz, _p]),
     "smrf_voxel_bounds_f64": (_i, [_p, _p, _p, _i64, C.POINTER(_d), C.POINTER(_i64), _p, _sz, _p]),
     "smrf_voxel_workspace_bytes": (_sz, [_i, _i, _i, _i]),

@@ -4,7 +4,7 @@
 :2642 and :2735 of the reference checkout).  The reference forms ``cdist`` and hands it to SciPy's
 ``linear_sum_assignment``; here one wave64 solves one problem out of LDS by shortest augmenting paths with float64 duals
 and, for ``bdr_bootstrap``, regresses the matched points straight away, all ``k`` samples in one launch
-(``csrc/assign.hip``, ``smrf_assign_*`` of ``include/smrf_assign.h``).  The contract - the cost bits, the tie rule, the summation order, the limit on
+(``csrc/assign.hip``, ``smrf_assign_*`` of ``include/smrf_hip.h``).  The contract - the cost bits, the tie rule, the summation order, the limit on
 the number of points - is DESIGN.md section 18.  NumPy in -> NumPy out; CUDA tensors in -> CUDA tensors out on their
 device.  float32 and integer coordinates are widened to float64.  There is no CPU fallback: without the library or a GPU
 every function raises :class:`neilpy_amd.SmrfHipError`.
@@ -27,38 +27,12 @@ from .points import _Cloud, _pair_check, _shape_check
 
 __all__ = ["hungarian_algorithm", "bdr", "bdr_bootstrap", "assignment_limit", "assignment_route"]
 
-# include/smrf_assign.h, the family's part of the C ABI: name -> (result, arguments).  Attached to the library on first use.
-_i, _i64, _sz, _p = C.c_int, C.c_int64, C.c_size_t, C.c_void_p
-SIGNATURES = {
-    "smrf_assign_limit": (_i, []),
-    "smrf_assign_workspace_bytes": (_sz, [_i64, _i64, _i]),
-    "smrf_assign_route": (_i, [_i64, _i64, _i, C.POINTER(_i)]),
-    "smrf_assign_solve_f64": (_i, [_p, _i64, _p, _i64, _i, _p, _p, _p, _p, _sz, _p]),
-    "smrf_assign_samples_check": (_i, [_p, _i64, _i64, _i64, C.POINTER(_i64), _p, _sz, _p]),
-    "smrf_assign_bdr_f64": (_i, [_p, _i64, _p, _i64, _p, _i64, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
-}
-_bound = None
-
-
-def _library():
-    """the loaded library with this family's prototypes attached; a library without them is an error"""
-    global _bound
-    lib = _lib.load()
-    if _bound is not lib:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)      # AttributeError if the export is missing
-            fn.restype = res
-            fn.argtypes = args
-        _bound = lib
-    return lib
-
-
 _SCALARS = ("beta1", "beta2", "alpha1", "alpha2", "rsquare", "D", "Dmax", "DI", "F")
 
 
 def assignment_limit():
     """The most points either side of one assignment problem may have (what fits one workgroup's LDS)."""
-    return int(_library().smrf_assign_limit())
+    return int(_lib.load().smrf_assign_limit())
 
 
 def assignment_route(nr, nc, d=2):
@@ -66,7 +40,7 @@ def assignment_route(nr, nc, d=2):
     in LDS), ``cached`` (the cost matrix is kept in LDS, not recomputed), ``waves`` per workgroup, ``lds_bytes`` per
     wave and ``cached_square``, the largest ``n`` whose ``n x n`` problem is cached."""
     r = (C.c_int * 5)()
-    _lib.check(_library().smrf_assign_route(int(nr), int(nc), int(d), r))
+    _lib.check(_lib.load().smrf_assign_route(int(nr), int(nc), int(d), r))
     return dict(register_columns=r[0], cached=bool(r[1]), waves=r[2], lds_bytes=r[3], cached_square=r[4])
 
 
@@ -77,7 +51,7 @@ def _limit_check(n, what):
 
 
 def _workspace(device, nr, nc, d):
-    return _torch().empty(_library().smrf_assign_workspace_bytes(nr, nc, d), dtype=_torch().uint8, device=device)
+    return _torch().empty(_lib.load().smrf_assign_workspace_bytes(nr, nc, d), dtype=_torch().uint8, device=device)
 
 
 def _status(ws):
@@ -107,8 +81,8 @@ def hungarian_algorithm(XY, AB):
     cols = torch.empty(n, dtype=torch.int64, device=x.t.device)
     costs = torch.empty(n, dtype=torch.float64, device=x.t.device)
     ws = _workspace(x.t.device, nr, nc, d)
-    _lib.check(_library().smrf_assign_solve_f64(_ptr(x.t), nr, _ptr(a.t), nc, d, _ptr(rows), _ptr(cols), _ptr(costs),
-                                                 _ptr(ws), ws.numel(), _stream()))
+    _lib.check(_lib.load().smrf_assign_solve_f64(_ptr(x.t), nr, _ptr(a.t), nc, d, _ptr(rows), _ptr(cols), _ptr(costs),
+                                                  _ptr(ws), ws.numel(), _stream()))
     _status(ws)
     if _is_tensor(XY):
         return rows, cols, costs
@@ -133,8 +107,8 @@ def _regress(x, a, samples, k, solve, full):
     else:
         rsq, di = new(k), new(k)
     ws = _workspace(dev, 1, 1, 2)
-    _lib.check(_library().smrf_assign_bdr_f64(_ptr(x.t), n, _ptr(a.t), a.n, _ptr(samples), k, int(solve), _ptr(scal),
-                                               _ptr(ap), _ptr(bp), _ptr(rsq), _ptr(di), _ptr(ws), ws.numel(), _stream()))
+    _lib.check(_lib.load().smrf_assign_bdr_f64(_ptr(x.t), n, _ptr(a.t), a.n, _ptr(samples), k, int(solve), _ptr(scal),
+                                                _ptr(ap), _ptr(bp), _ptr(rsq), _ptr(di), _ptr(ws), ws.numel(), _stream()))
     if solve:
         _status(ws)
     return (scal, ap, bp) if full else (rsq, di)
@@ -179,8 +153,8 @@ def _sample_table(samples, n, m, device):
         t = _h2d(np.ascontiguousarray(arr, dtype=np.int64))
     ws = _workspace(device, 1, 1, 2)
     bad = C.c_int64(0)
-    _lib.check(_library().smrf_assign_samples_check(_ptr(t), shape[0], n, m, C.byref(bad), _ptr(ws), ws.numel(),
-                                                     _stream()))
+    _lib.check(_lib.load().smrf_assign_samples_check(_ptr(t), shape[0], n, m, C.byref(bad), _ptr(ws), ws.numel(),
+                                                      _stream()))
     if bad.value:
         raise ValueError("samples: %d entries are not rows of AB (0 .. %d)" % (bad.value, m - 1))
     return t

@@ -27,7 +27,6 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import _lib
 from ._device import device_scoped as _device_scoped
 from ._raster import Raster, _ptr, _torch
 from .api import _has_nan
@@ -35,7 +34,7 @@ from .api import _has_nan
 __all__ = ["grey_erosion", "grey_dilation", "grey_opening", "grey_closing", "white_tophat", "black_tophat",
            "morphological_gradient", "rectangle", "square", "diamond", "plan"]
 
-# include/smrf_footprint.h, the family's part of the C ABI: border modes, the paths ``impl=`` forces (FORCE_NAN_AWARE is
+# include/smrf_hip.h, the family's part of the C ABI: border modes, the paths ``impl=`` forces (FORCE_NAN_AWARE is
 # this module's own flag on top: the NaN-aware launch whatever the raster holds), store epilogues, the LDS cap of the
 # runs path and the least member count of an automatic runs launch
 REFLECT, NEAREST = 0, 1
@@ -43,30 +42,6 @@ IMPL_AUTO, IMPL_RUNS, IMPL_TAPS, FORCE_NAN_AWARE = 0, 1, 2, 4
 STORE, SUB_MINUS, MINUS_SUB, GRADIENT = range(4)
 TILE_BYTES = 53248
 RUNS_MIN_TAPS = 9
-
-# name -> (result, arguments).  Attached to the library on first use.
-_i, _p = C.c_int, C.c_void_p
-SIGNATURES = {
-    "smrf_footprint_tile_bytes": (_i, []),
-    "smrf_footprint_path": (_i, [_p, _i, _i, _i]),
-    "smrf_footprint_filter_f32": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _i, _p]),
-    "smrf_footprint_filter_f64": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _i, _p]),
-}
-_bound = None
-
-
-def _library():
-    """the loaded library with this family's prototypes attached; a library without them is an error"""
-    global _bound
-    lib = _lib.load()
-    if _bound is not lib:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)      # AttributeError if the export is missing
-            fn.restype = res
-            fn.argtypes = args
-        _bound = lib
-    return lib
-
 
 TX, TY = 64, 8                 # the workgroup's cells (csrc/footprint.hip)
 MAX_LEVELS = 16                # slots of the plan's head
@@ -132,7 +107,7 @@ def plan(footprint, dilate=False, mode="reflect", itemsize=4, gradient=False, im
     ``lds_bytes``  what the planes take (twice for ``gradient``, which keeps a min and a max set);
     ``path``       ``'runs'`` or ``'taps'`` as the library will choose under ``impl``, ``'refused'`` where RUNS is
                    forced past ``cap``;
-    ``head``, ``table``      the int32 arrays the entry point takes (include/smrf_footprint.h).
+    ``head``, ``table``      the int32 arrays the entry point takes (include/smrf_hip.h).
     """
     if mode not in MODES:
         raise NotImplementedError("mode %r: only 'reflect' and 'nearest' are supported on the device" % (mode,))
@@ -246,7 +221,6 @@ class _Filter:
         if R.t.numel():
             P = plan(self.fp, dilate, itemsize=R.t.element_size(), gradient=epilogue == GRADIENT)
             table = _torch().from_numpy(P.table).to(R.t.device)
-            _library()
             R.call("footprint_filter", _ptr(src), _ptr(sub), _ptr(out), R.rows, R.cols, _ptr(table),
                    P.head.ctypes.data_as(C.c_void_p), int(dilate), self.mode, int(self.nan_aware), self.impl, epilogue)
             # the table is freed by the caching allocator on this stream only after the launch has read it

@@ -1,5 +1,5 @@
 """The case table of the kernel families (a plain helper module, no test in it): what tests/test_gpu_guarded.py,
-tests/test_gpu_streams.py and tests/test_gpu_threads.py share.
+tests/test_gpu_streams.py, tests/test_gpu_views.py and tests/test_gpu_threads.py share.
 
 The package's exports are classified here (tests/test_guarded_host.py compares the lists with neilpy_amd's namespace), and
 every name of GUARDED has a *builder*: a generator ``builder(names, **selection)`` of case dicts
@@ -27,6 +27,7 @@ import numpy as np
 import pytest
 
 import focal_numpy as fnp
+import footprint_numpy as fpn
 import morph_numpy as mn
 import morphometry_numpy as mnp
 import nearest_numpy as nn
@@ -50,14 +51,17 @@ GUARDED = ("slope", "aspect", "hillshade", "multiple_illumination", "esri_slope"
            "raster_stats", "normalize", "rmse", "colortable_shade", "swiss_shading", "brassel_atmospheric_perspective",
            "progressive_filter", "erosion", "dilation", "opening",
            "create_dem", "inpaint_nearest", "nearest_source", "inpaint_nans_by_springs", "inpaint_nans_by_fda",
-           "nearest_points", "chamfer_distance", "voxelize", "pssm", "smrf", "read_las_xyz")
+           "nearest_points", "chamfer_distance", "voxelize", "pssm", "smrf", "read_las_xyz",
+           "hungarian_algorithm", "bdr", "bdr_bootstrap",
+           "grey_erosion", "grey_dilation", "grey_opening", "grey_closing", "white_tophat", "black_tophat",
+           "morphological_gradient")
 # launches a kernel and has no builder: name -> reason
 LEFT_OUT = {}
 # exported and launches nothing: host helpers, constants, views and table look-ups by torch indexing
 NO_KERNEL = ("SmrfHipError", "load_library", "LIB_PATH", "Affine", "edges_from_IT", "from_origin", "write_worldfile", "disk",
              "last_stats", "distance_kernel", "read_las", "write_las", "triangle_height", "cutter", "z_factor", "synth_dem",
              "synth_points", "geomorphon_cmap", "get_lowest_equivalent", "int2base", "progressive_window",
-             "terrain_code_to_geomorphon")
+             "terrain_code_to_geomorphon", "rectangle", "square", "diamond")
 
 # Returned tensors that do not live in an arena: (function, path of the leaf in the result) -> the torch op that made it.
 # Every entry names a torch op, not a kernel; an entry whose tensor IS owned fails too, so the table cannot go stale.
@@ -71,14 +75,16 @@ NOT_OWNED = {
 SURFACE = tuple(sorted(sn.FUNCS))
 TERRAIN = ("openness", "skyview_factor", "count_openness", "geomorphons", "ternary_pattern_from_openness")
 DISK = ("erosion", "dilation", "opening")
+MORPHOLOGY = tuple(fpn.FUNCTIONS)
 
 DEVICE = "cuda:0"
 AUTO, TILED, DIRECT = IMPLS = 0, 1, 2         # every wrapper's default is AUTO: a call without impl= is the AUTO case
+RUNS = 1                                      # grey morphology's name for impl 1 (2 is its taps path)
 F32, F64 = np.float32, np.float64
 
 
 def F(name):
-    """a guarded export by name: as a literal name, or as F(fn) with fn drawn from SURFACE, TERRAIN or DISK -
+    """a guarded export by name: as a literal name, or as F(fn) with fn drawn from SURFACE, TERRAIN, DISK or MORPHOLOGY -
     tests/test_guarded_host.py reads GUARDED against exactly these in this file's source"""
     import neilpy_amd
     assert name in GUARDED, name
@@ -646,6 +652,51 @@ def points(names, ds=(2, 3)):
             if "chamfer_distance" in names:
                 yield case("chamfer_distance", lambda qt, pt: F("chamfer_distance")(qt, pt), [q, p], (n, d), stream=(d, n) == (2, 257),
                            reference=lambda got, q=q, p=p, n=n: chamfer_close(got, pn.chamfer_distance(q, p), n + len(q)))
+
+
+@builds("hungarian_algorithm", "bdr", "bdr_bootstrap")
+def matching(names):
+    """70 against 300 points of dimension 3 for the assignment, 65 pairs for the regression, 30 of 60 points under a
+    7-row sample table for the bootstrap; every device-formed value has the bits of tests/assign_numpy.py.  stream: all three"""
+    import assign_cases as ac
+    import assign_numpy as an
+    from test_gpu_assign import assert_bits
+    x, a = ac.random_pair(70, 300, 3, 60)
+    bx, ba = ac.random_pair(65, 65, 2, 61)
+    sx, sa = ac.random_pair(30, 60, 2, 62)
+    ba, sa = ba + 0.7 * bx, sa + 0.5 * np.vstack([sx, sx])
+    table = np.stack([np.random.default_rng(63 + s).permutation(60)[:30] for s in range(7)]).astype(np.int64)
+    if "hungarian_algorithm" in names:
+        yield case("hungarian_algorithm", lambda xt, at: F("hungarian_algorithm")(xt, at), [x, a], (70, 300, 3), stream=True,
+                   reference=lambda got: assert_bits(got, an.hungarian_algorithm(x, a), range(3), "hungarian_algorithm"))
+    if "bdr" in names:
+        yield case("bdr", lambda xt, at: F("bdr")(xt, at), [bx, ba], 65, stream=True,
+                   reference=lambda got: assert_bits(got, an.bdr(bx, ba), an.SCALARS, "bdr"))
+    if "bdr_bootstrap" in names:
+        yield case("bdr_bootstrap", lambda xt, at, tt: F("bdr_bootstrap")(xt, at, samples=tt), [sx, sa, table], (30, 60, 7),
+                   stream=True, reference=lambda got: assert_bits(got, an.bdr_bootstrap(sx, sa, table), range(2), "bdr_bootstrap"))
+
+
+@builds(*MORPHOLOGY)
+def morphology(names, dtypes=(F32, F64)):
+    """three footprints of tests/test_gpu_footprint.py - rand4x7 (even-sized and not its own mirror image: the gradient takes
+    two launches), diamond5 (one) and L7x4 - under 'reflect' on every raster, under 'nearest' once per name, every impl
+    (a forced runs launch the plan refuses is left to that module).  stream: the NaN raster, rand4x7, 'reflect', AUTO"""
+    from test_gpu_footprint import assert_same, footprints, reference, runs_refused
+    fps = {tag: fp for tag, fp in footprints().items() if tag in ("rand4x7", "diamond5", "L7x4")}
+    for Z, ctx in cases_of(TILE_SHAPES, dtypes):
+        for tag, fp in fps.items():
+            nearest_too = tag == "rand4x7" and ctx[0] == NAN_SHAPE and "nan" not in ctx
+            for mode in ("reflect", "nearest") if nearest_too else ("reflect",):
+                for fn in names:
+                    want = once(lambda fn=fn, Z=Z, fp=fp, mode=mode: reference(fn, Z, fp, mode))
+                    for impl in IMPLS if mode == "reflect" else (AUTO,):
+                        if impl == RUNS and runs_refused(fn, fp, Z.dtype):
+                            continue
+                        c = (ctx, tag, mode, impl)
+                        yield case(fn, lambda Zt, fn=fn, fp=fp, mode=mode, impl=impl: F(fn)(Zt, footprint=fp, mode=mode, impl=impl),
+                                   [Z], c, lambda got, want=want, c=c: assert_same(got, want(), c),
+                                   stream="nan" in ctx and (tag, mode, impl) == ("rand4x7", "reflect", AUTO))
 
 
 @builds("voxelize")

@@ -133,39 +133,13 @@ def test_bootstrap_restatement_against_reference(G):
             assert err <= bounds[key][1], (name, key, err)
 
 
-# ---- the C ABI, without a GPU: the family's header, then sizing, argument and workspace errors by status code -----
-def test_abi_header_and_prototypes():
-    """include/smrf_assign.h is part of include/smrf_hip.h; what tests/test_abi.py and tests/test_streamed_host.py ask of
-    that header's declarations is asked of this one's here: every declared entry is exported and has its prototype in
-    neilpy_amd/matching.py with as many arguments, and every entry that launches takes ``void* stream`` last"""
-    import ctypes as C
-    import os
-    import re
-    import streamed as S
-    from conftest import ROOT
-    from neilpy_amd import _lib, matching
-    main = open(os.path.join(ROOT, "include", "smrf_hip.h")).read()
-    assert main.count('#include "smrf_assign.h"') == 1
-    text = open(os.path.join(ROOT, "include", "smrf_assign.h")).read()
-    decl, slots = S.declarations(text), S.stream_slots(text)
-    assert set(decl) == set(matching.SIGNATURES) and len(decl) == 6 and all(n.startswith("smrf_assign_") for n in decl)
-    assert not set(decl) & set(_lib.SIGNATURES)
-    lib = matching._library()
-    no_launch = re.compile(r"^smrf_assign_(workspace_bytes|limit|route)$")
-    for name, params in decl.items():
-        res, args = matching.SIGNATURES[name]
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args) and len(args) == len(params), name
-        if no_launch.match(name):
-            assert slots[name] is None, name
-        else:
-            assert slots[name] == len(params) - 1 and args[-1] is C.c_void_p, name + " launches: the stream comes last"
-    assert sum(1 for n in decl if not no_launch.match(n)) == 3
-
-
+# ---- the C ABI, without a GPU: sizing, argument and workspace errors by status code -----
 def test_abi_sizes_and_route():
-    from neilpy_amd.matching import _library
-    lib = _library()
+    import streamed as S
+    from neilpy_amd import _lib
+    lib = _lib.load()
+    assert {n for n in S.declarations() if n.startswith("smrf_assign_")} == {"smrf_assign_" + n for n in (
+        "limit", "workspace_bytes", "route", "solve_f64", "samples_check", "bdr_f64")}
     limit = lib.smrf_assign_limit()
     assert limit >= 1024
     assert lib.smrf_assign_workspace_bytes(1, 1, 2) > 0 and lib.smrf_assign_workspace_bytes(limit, limit, 3) > 0
@@ -189,8 +163,8 @@ def test_abi_sizes_and_route():
 
 def test_abi_argument_errors():
     import ctypes as C
-    from neilpy_amd.matching import _library
-    lib = _library()
+    from neilpy_amd import _lib
+    lib = _lib.load()
     p = C.c_void_p(4096)                                            # never dereferenced: every call is refused first
     null = C.c_void_p(0)
     limit = lib.smrf_assign_limit()
@@ -225,7 +199,7 @@ def test_public_names_and_no_cpu_fallback():
     import neilpy_amd
     na = neilpy_amd.matching
     for name in ("hungarian_algorithm", "bdr", "bdr_bootstrap"):
-        assert callable(getattr(na, name)) and name in na.__all__
+        assert callable(getattr(na, name)) and name in na.__all__ and getattr(neilpy_amd, name) is getattr(na, name)
     x, a = ac.random_pair(5, 5, 2, 9)
     # shape errors need no GPU: they are raised before anything is uploaded
     with pytest.raises(ValueError):
@@ -239,3 +213,19 @@ def test_public_names_and_no_cpu_fallback():
     if not torch.cuda.is_available():
         with pytest.raises(neilpy_amd.SmrfHipError):
             na.hungarian_algorithm(x, a)
+
+
+def test_the_case_table_holds_inputs_the_restatement_accepts():
+    """tests/family_cases.py's matching cases, walked without a GPU: each case's reference passes on the restatement's own
+    result for its inputs, the assignment's optimum is unique (SciPy's assignment is the restatement's), and every name
+    has a case for the stream and view runs"""
+    import family_cases as FC
+    names = ("hungarian_algorithm", "bdr", "bdr_bootstrap")
+    marked = set()
+    for case in FC.matching(names):
+        got = getattr(an, case["name"])(*case["inputs"])
+        case["reference"](FC.rebuild(got, FC.to_numpy))
+        marked |= {case["name"]} if case["stream"] else set()
+        if case["name"] == "hungarian_algorithm":
+            assert all(an.same_bits(p, q) for p, q in zip(got, ac.scipy_assignment(*case["inputs"])))
+    assert marked == set(names)

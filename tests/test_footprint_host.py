@@ -189,11 +189,19 @@ def test_plan_path_follows_the_cap_and_the_library():
     """past the LDS cap the automatic path is taps and a forced runs launch is refused; the library's own decision
     (smrf_footprint_path, host logic) is the plan's for every footprint, dtype, epilogue and impl"""
     import ctypes as C
-    from neilpy_amd import morphology as mo
+    from neilpy_amd import _lib, morphology as mo
     square = mo.square
-    lib = mo._library()
+    lib = _lib.load()
     cap = lib.smrf_footprint_tile_bytes()
     assert cap == mo.TILE_BYTES
+    header = open(os.path.join(ROOT, "include", "smrf_hip.h")).read()
+    for c_name, value in (("SMRF_FOOTPRINT_RUNS_MIN_TAPS", mo.RUNS_MIN_TAPS), ("SMRF_FOOTPRINT_TILE_BYTES", mo.TILE_BYTES),
+                          ("SMRF_FOOTPRINT_IMPL_AUTO", mo.IMPL_AUTO), ("SMRF_FOOTPRINT_IMPL_RUNS", mo.IMPL_RUNS),
+                          ("SMRF_FOOTPRINT_IMPL_TAPS", mo.IMPL_TAPS), ("SMRF_FOOTPRINT_REFLECT", mo.REFLECT),
+                          ("SMRF_FOOTPRINT_NEAREST", mo.NEAREST), ("SMRF_FOOTPRINT_STORE", mo.STORE),
+                          ("SMRF_FOOTPRINT_SUB_MINUS", mo.SUB_MINUS), ("SMRF_FOOTPRINT_MINUS_SUB", mo.MINUS_SUB),
+                          ("SMRF_FOOTPRINT_GRADIENT", mo.GRADIENT), ("SMRF_FOCAL_TILE_BYTES", mo.TILE_BYTES)):   # one cap
+        assert int(re.search(r"#define %s (\d+)" % c_name, header).group(1)) == value, c_name
     for itemsize in (4, 8):
         w = 1
         while mo.plan(square(w + 1), itemsize=itemsize, cap=cap).lds_bytes <= cap:
@@ -226,6 +234,7 @@ def test_signatures_are_scipys_plus_keyword_only():
     import neilpy_amd
     mo = neilpy_amd.morphology                              # the package imports the module
     assert set(NAMES) | {"rectangle", "square", "diamond", "plan"} == set(mo.__all__)
+    assert all(getattr(neilpy_amd, n) is getattr(mo, n) for n in mo.__all__ if n != "plan") and not hasattr(neilpy_amd, "plan")
     for name in NAMES:
         positional = lambda f: [(p.name, p.kind, p.default) for p in inspect.signature(f).parameters.values()
                                 if p.kind is not inspect.Parameter.KEYWORD_ONLY]
@@ -294,7 +303,7 @@ def test_disk_only_functions_still_refuse_other_footprints():
 
 
 # ------------------------------------------------------------------------------------------
-# helpers and the ABI
+# helpers, the case table and the ABI
 # ------------------------------------------------------------------------------------------
 def test_helpers():
     from neilpy_amd import disk
@@ -312,38 +321,22 @@ def test_helpers():
     assert np.array_equal(diamond(1), disk(1))
 
 
-def test_abi_header_and_prototypes():
-    """include/smrf_footprint.h is part of include/smrf_hip.h; what tests/test_abi.py and tests/test_streamed_host.py
-    ask of that header's declarations is asked of this one's here: every declared entry is exported and has its
-    prototype in neilpy_amd/morphology.py with as many arguments, and the entries that launch take ``void* stream``
-    last"""
-    import ctypes as C
-    import streamed as S
-    from neilpy_amd import _lib, morphology as mo
-    main = open(os.path.join(ROOT, "include", "smrf_hip.h")).read()
-    assert main.count('#include "smrf_footprint.h"') == 1
-    text = open(os.path.join(ROOT, "include", "smrf_footprint.h")).read()
-    decl, slots = S.declarations(text), S.stream_slots(text)
-    assert set(decl) == set(mo.SIGNATURES) and len(decl) == 4 and all(n.startswith("smrf_footprint_") for n in decl)
-    assert not set(decl) & set(_lib.SIGNATURES)
-    lib = mo._library()
-    for name, params in decl.items():
-        res, args = mo.SIGNATURES[name]
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args) and len(args) == len(params), name
-        if name.startswith("smrf_footprint_filter_"):
-            assert slots[name] == len(params) - 1 == 12 and args[-1] is C.c_void_p, name
-        else:
-            assert slots[name] is None, name
-    for c_name, value in (("SMRF_FOOTPRINT_RUNS_MIN_TAPS", mo.RUNS_MIN_TAPS), ("SMRF_FOOTPRINT_TILE_BYTES", mo.TILE_BYTES),
-                          ("SMRF_FOOTPRINT_IMPL_AUTO", mo.IMPL_AUTO), ("SMRF_FOOTPRINT_IMPL_RUNS", mo.IMPL_RUNS),
-                          ("SMRF_FOOTPRINT_IMPL_TAPS", mo.IMPL_TAPS), ("SMRF_FOOTPRINT_REFLECT", mo.REFLECT),
-                          ("SMRF_FOOTPRINT_NEAREST", mo.NEAREST), ("SMRF_FOOTPRINT_STORE", mo.STORE),
-                          ("SMRF_FOOTPRINT_SUB_MINUS", mo.SUB_MINUS), ("SMRF_FOOTPRINT_MINUS_SUB", mo.MINUS_SUB),
-                          ("SMRF_FOOTPRINT_GRADIENT", mo.GRADIENT)):
-        assert int(re.search(r"#define %s (\d+)" % c_name, text).group(1)) == value, c_name
-    assert int(re.search(r"#define SMRF_FOCAL_TILE_BYTES (\d+)", main).group(1)) == mo.TILE_BYTES   # one cap, one reasoning
-    assert lib.smrf_footprint_tile_bytes() == mo.TILE_BYTES and lib.smrf_abi_version() == 1
+def test_the_case_table_holds_inputs_the_references_accept():
+    """tests/family_cases.py's morphology cases, walked without a GPU: each case's reference (SciPy where it is the
+    oracle) passes on the restatement's result for that raster, footprint and mode, and every name and dtype has a case for
+    the stream and view runs"""
+    import family_cases as FC
+    from test_gpu_footprint import footprints
+    fps, restated, marked = footprints(), {}, set()
+    for case in FC.morphology(NAMES):
+        (X,), (ctx, tag, mode, impl) = case["inputs"], case["ctx"]
+        key = (case["name"], ctx, tag, mode)
+        if key not in restated:
+            restated[key] = fpn.FUNCTIONS[case["name"]](X, fps[tag], mode)
+        case["reference"](restated[key])
+        marked |= {(case["name"], X.dtype.type)} if case["stream"] else set()
+    assert marked == {(n, t) for n in NAMES for t in (np.float32, np.float64)}
+    assert {k[2:] for k in restated} == {(t, "reflect") for t in ("rand4x7", "diamond5", "L7x4")} | {("rand4x7", "nearest")}
 
 
 def test_kernels_compile_without_scratch(tmp_path):
@@ -357,8 +350,11 @@ def test_kernels_compile_without_scratch(tmp_path):
 def test_abi_argument_errors():
     """refusals by status code, before any launch and so without a GPU"""
     import ctypes as C
-    from neilpy_amd import morphology as mo
-    lib = mo._library()
+    import streamed as S
+    from neilpy_amd import _lib, morphology as mo
+    lib = _lib.load()
+    assert {n for n in S.declarations() if n.startswith("smrf_footprint_")} == {"smrf_footprint_" + n for n in (
+        "tile_bytes", "path", "filter_f32", "filter_f64")}
     p, null = C.c_void_p(4096), C.c_void_p(0)                        # never dereferenced: every call is refused first
     head = mo.plan(np.ones((3, 3))).head
     h = head.ctypes.data_as(C.c_void_p)

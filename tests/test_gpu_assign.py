@@ -12,7 +12,7 @@ import pytest
 import assign_cases as ac
 import assign_numpy as an
 from conftest import golden
-from guarded import POISONS, guarded, same_bits
+from guarded import POISONS, guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -22,6 +22,13 @@ K = 64
 @pytest.fixture(scope="module")
 def G():
     return golden("assign.npz")
+
+
+def assert_bits(got, want, keys, ctx):
+    """the entries ``keys`` of a result - positions of a tuple, fields of bdr's dict - have the bits of ``want``'s: what
+    tests/family_cases.py's matching cases compare with the restatement"""
+    for k in keys:
+        assert an.same_bits(got[k], want[k]), (ctx, k, got[k], want[k])
 
 
 def check_hungarian(x, a, want=None):
@@ -206,76 +213,6 @@ def test_bootstrap_beyond_the_register_columns(gpu_device):
     r, d = na.bdr_bootstrap(xy, ab, samples=table)
     w = an.bdr_bootstrap(xy, ab, table)
     assert an.same_bits(r, w[0]) and an.same_bits(d, w[1])
-
-
-# every public call, once under tests/guarded.py with both poisons
-def _calls():
-    x, a = ac.random_pair(70, 300, 3, 60)
-    bx, ba = ac.random_pair(65, 65, 2, 61)
-    sx, sa = ac.random_pair(30, 60, 2, 62)
-    table = np.stack([np.random.default_rng(63 + s).permutation(60)[:30] for s in range(7)]).astype(np.int64)
-    return x, a, bx, ba + 0.7 * bx, sx, sa + 0.5 * np.vstack([sx, sx]), table
-
-
-GUARDED_CALLS = {
-    "hungarian_algorithm": lambda na, c, t: na.hungarian_algorithm(t(c[0]), t(c[1])),
-    "bdr": lambda na, c, t: na.bdr(t(c[2]), t(c[3])),
-    "bdr_bootstrap": lambda na, c, t: na.bdr_bootstrap(t(c[4]), t(c[5]), samples=t(c[6])),
-}
-
-
-def _leaves(res):
-    vals = list(res.values()) if isinstance(res, dict) else list(res)
-    return [v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v) for v in vals]
-
-
-@pytest.mark.parametrize("name", sorted(GUARDED_CALLS))
-def test_guarded(gpu_device, name):
-    from neilpy_amd import matching as na
-    c = _calls()
-    runs = []
-    for poison in POISONS:
-        with guarded(gpu_device, poison) as g:
-            made = []
-
-            def t(array):
-                made.append(g.tensor(array))
-                return made[-1]
-            res = GUARDED_CALLS[name](na, c, t)
-            out = _leaves(res)
-        g.check()
-        assert made and all(g.unchanged(m) for m in made)
-        runs.append(out)
-    assert len(runs[0]) == len(runs[1]) and all(same_bits(p, q) for p, q in zip(*runs))
-    want = {"hungarian_algorithm": lambda: list(an.hungarian_algorithm(c[0], c[1])),
-            "bdr": lambda: None,
-            "bdr_bootstrap": lambda: list(an.bdr_bootstrap(c[4], c[5], c[6]))}[name]()
-    if want is not None:
-        assert all(an.same_bits(p, q) for p, q in zip(runs[0], want))
-    else:
-        w = an.bdr(c[2], c[3])
-        got = dict(zip(("beta1", "beta2", "alpha1", "alpha2", "rsquare", "D", "Dmax", "DI", "F"), runs[0]))
-        assert all(an.same_bits(got[k], w[k]) for k in got)
-
-
-def test_side_stream(gpu_device, boot):
-    """each call with a side stream current, the default stream busy with something else"""
-    import torch
-    from neilpy_amd import matching as na
-    x, a, seed, table, wr, wd = boot["30of60"]
-    side = torch.cuda.Stream(device=gpu_device)
-    busy = torch.ones(1 << 22, device=gpu_device)
-    with torch.cuda.stream(side):
-        for _ in range(4):
-            busy = busy * 1.0001
-        rsq, di = na.bdr_bootstrap(x, a, samples=table)
-        rows, cols, mc = na.hungarian_algorithm(x, a)
-        r = na.bdr(x, a[:30])
-    side.synchronize()
-    assert an.same_bits(rsq, wr) and an.same_bits(di, wd)
-    wrow, wcol, wm = an.hungarian_algorithm(x, a)
-    assert np.array_equal(rows, wrow) and np.array_equal(cols, wcol) and an.same_bits(mc, wm)
-    assert an.same_bits(r["rsquare"], an.bdr(x, a[:30])["rsquare"])
 
 
 def test_errors(gpu_device):

@@ -227,6 +227,17 @@ def test_points(gpu_device, d):
     run_all(FC.points(("nearest_points", "chamfer_distance"), (d,)))
 
 
+@pytest.mark.parametrize("fn", ["hungarian_algorithm", "bdr", "bdr_bootstrap"])
+def test_matching(gpu_device, fn):
+    run_all(FC.matching((fn,)))
+
+
+@pytest.mark.parametrize("dtype", [F32, F64])
+def test_morphology(gpu_device, dtype):
+    """three footprints, both border modes, the runs and the taps path: one and two launches per function"""
+    run_all(FC.morphology(FC.MORPHOLOGY, (dtype,)))
+
+
 @pytest.mark.parametrize("T", [F32, F64])
 def test_voxelize(gpu_device, T):
     run_all(FC.voxelize(("voxelize",), (T,)))

@@ -17,11 +17,11 @@ any D):
     torch.cuda._sleep runs 2.39 M cycles per millisecond.  On each of four fresh streams, 10 repetitions per delay:
     stand-ins (a) and (b) were caught 10 of 10 from 4 ms down to 0.0625 ms, (a) 9 of 10 on one stream at 0.03125 ms, none at
     0.015625 ms; (c) and the correct stand-in were judged right at every delay.  The detection threshold is 0.0625 ms,
-    which makes 0.25 ms the smallest D that is caught at D and at D / 4.  D is set to 1 ms = 2 386 775 cycles, four times
+    which makes 0.25 ms the smallest D that is caught at D and at D / 4.  D is set to 1 ms = 2 401 742 cycles, four times
     that: test_standins repeats the proof at D / 4 in every run, and at D = 1 ms that repetition runs at 0.25 ms, fourfold
     above the threshold instead of on it (what sets the threshold is how fast the host enqueues, which a busier machine
-    does more slowly).  Side stream: candidate 0 of 4 (all four qualified).  376 redirected allocations per module run,
-    each behind one delay; the module takes 5.1 s (tests/test_gpu_threads.py: 5.1 s).
+    does more slowly).  Side stream: candidate 0 of 4 (all four qualified).  439 redirected allocations per module run,
+    each behind one delay; the module takes 4.6 s (tests/test_gpu_threads.py: 5.1 s).
 Mutants, run once on a scratch copy: with ``_raster._stream()`` returning handle 0 all 65 cases of the 26 names whose
 scratch planes hold values only (surface, focal, terrain, morphometry, disk filters, progressive_filter) failed on the
 handle check; the other families were not run under that mutant, since a poisoned index plane read by a kernel on the

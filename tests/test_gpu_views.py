@@ -15,9 +15,9 @@ how the caller's arrays lie in memory, nothing else.
 contract DESIGN.md section 1 and include/smrf_hip.h state; ``smrf_voxel_expand``, the one entry point that asks for more
 (of ``d_out``), refuses such a pointer with SMRF_E_ARG (test_an_entry_point_that_needs_more_refuses).
 
-Measured on an MI355X (the module prints these figures): 96 cases, 1106 calls under a layout (every layout under both
-poisons, after the plain call: 12 for a raster case, 10 for one that fills its argument, 8 for the vector clouds of
-create_dem, voxelize and smrf), 3.6 s from the first case to the last (tests/test_gpu_streams.py: 5.1 s).  The layouts
+Measured on an MI355X (the module prints these figures): 113 cases, 1310 calls under a layout (every layout under both
+poisons, after the plain call: 12 for a raster or (n, d) cloud case, 10 for one that fills its argument, 8 for the vector
+clouds of create_dem, voxelize and smrf), 2.9 s from the first case to the last (tests/test_gpu_streams.py: 4.6 s).  The layouts
 found one wrong read: the band driver counted a strided band's NaNs through its data pointer
 (test_a_strided_band_counts_its_own_nans).
 Mutants, run once on a scratch copy, each layout of each case judged on its own:

@@ -210,10 +210,9 @@ def test_every_export_is_guarded_left_out_with_a_reason_or_launches_nothing():
                                                         sorted((lists[0] | lists[1] | lists[2]) - exports))
     assert all(isinstance(r, str) and r for r in T.LEFT_OUT.values())
     assert set(T.BUILDERS) == lists[0], sorted(set(T.BUILDERS) ^ lists[0])
-    # every guarded name is really called: as the literal F("name"), or as F(fn) over one of the three tuples
+    # every guarded name is really called: as the literal F("name"), or as F(fn) over one of the four tuples
     src = open(T.__file__.rstrip("c")).read()
-    literal = set(re.findall(r'\bF\("(\w+)"\)', src))
+    called = set(re.findall(r'\bF\("(\w+)"\)', src)) | set(T.SURFACE) | set(T.TERRAIN) | set(T.DISK) | set(T.MORPHOLOGY)
     assert "F(fn)" in src
-    assert literal | set(T.SURFACE) | set(T.TERRAIN) | set(T.DISK) == lists[0], \
-        sorted(lists[0] ^ (literal | set(T.SURFACE) | set(T.TERRAIN) | set(T.DISK)))
+    assert called == lists[0], sorted(lists[0] ^ called)
     assert all(isinstance(r, str) and r for r in T.NOT_OWNED.values())
