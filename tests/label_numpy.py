@@ -1,6 +1,7 @@
 """The contract of neilpy_amd/label.py restated in NumPy and plain Python (a plain helper module, no test in it, and no
 import of the package): union-find to the minimum linear index, numbering of the roots by rank,
-sizes, boxes, and the masks the tests are run on.  tests/test_label_host.py pins it to scipy.ndimage."""
+sizes, boxes, and the masks the tests are run on, constructed ones and seeded random ones with structure.
+tests/test_label_host.py pins it to scipy.ndimage."""
 import numpy as np
 
 E, S, SE, SW = 1, 2, 4, 8
@@ -180,6 +181,66 @@ def constructed(shape):
     return {"ones": np.ones(shape, dtype=bool), "zeros": np.zeros(shape, dtype=bool), "checkerboard": checkerboard(shape),
             "serpentine": serpentine(shape), "spiral": spiral(shape), "comb": comb(shape), "stripes se": stripes(shape, 1),
             "stripes sw": stripes(shape, -1), "u and speck": u_and_speck(shape), "frame": frame(shape)}
+
+
+# ------------------------------------------------------------------------------------------
+# structured random masks: a shape and a seed each, NumPy and SciPy only, 1 x N and N x 1 included
+# ------------------------------------------------------------------------------------------
+def _rng(name, shape, seed):
+    return np.random.default_rng([20270206, sum(map(ord, name)), seed] + list(shape))
+
+
+def blobs(shape, seed):
+    """box-smoothed noise above its median: solid objects some tens of cells across, with holes, that cross the seams"""
+    import scipy.ndimage as ndi
+    smooth = ndi.uniform_filter(_rng("blobs", shape, seed).random(shape), size=9, mode="reflect")
+    return smooth > np.median(smooth)
+
+
+def strokes(shape, seed):
+    """thick segments at random angles: 1 to 4 cells thick, up to the raster's length long"""
+    rng = _rng("strokes", shape, seed)
+    rows, cols = shape
+    a = np.zeros(shape, dtype=bool)
+    t = np.linspace(0.0, 1.0, 2 * max(rows, cols) + 1)
+    for _ in range(4 + (rows + cols) // 16):
+        (r0, r1), (c0, c1), thick = rng.random(2) * (rows - 1), rng.random(2) * (cols - 1), int(rng.integers(1, 5))
+        r, c = np.rint(r0 + (r1 - r0) * t).astype(int), np.rint(c0 + (c1 - c0) * t).astype(int)
+        for dr in range(thick):
+            for dc in range(thick):
+                a[np.minimum(r + dr, rows - 1), np.minimum(c + dc, cols - 1)] = True
+    return a
+
+
+def rings(shape, seed):
+    """concentric rings about a drawn centre, 1 to 4 cells wide and as far apart: objects in the holes of others"""
+    rng = _rng("rings", shape, seed)
+    r, c = np.indices(shape)
+    width = int(rng.integers(1, 5))
+    d = np.hypot(r - rng.random() * (shape[0] - 1), c - rng.random() * (shape[1] - 1))
+    return np.floor(d / width).astype(np.int64) % 2 == 0
+
+
+def maze(shape, seed):
+    """a random spanning tree of the cells at even rows and columns, the passages between joined cells opened: one
+    4-connected object of one-cell corridors with no loop, so its union chains are long and winding"""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import minimum_spanning_tree
+    rng = _rng("maze", shape, seed)
+    rows, cols = shape
+    gr, gc = (rows + 1) // 2, (cols + 1) // 2
+    node = np.arange(gr * gc).reshape(gr, gc)
+    a = np.zeros(shape, dtype=bool)
+    a[::2, ::2] = True
+    u = np.concatenate([node[:, :-1].ravel(), node[:-1, :].ravel()])
+    v = np.concatenate([node[:, 1:].ravel(), node[1:, :].ravel()])
+    if u.size:
+        tree = minimum_spanning_tree(coo_matrix((rng.random(u.size) + 0.5, (u, v)), shape=(node.size, node.size))).tocoo()
+        a[tree.row // gc + tree.col // gc, tree.row % gc + tree.col % gc] = True       # the cell between the two
+    return a
+
+
+GENERATORS = {f.__name__: f for f in (blobs, strokes, rings, maze)}
 
 
 # a hand-made label raster: gaps (3 and 6 do not occur), a label above any max_label a test passes (40), negative cells

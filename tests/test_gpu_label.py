@@ -2,7 +2,8 @@
 structures against scipy.ndimage.label on shapes that straddle every tile edge, on random masks near and far from the
 percolation thresholds and on constructed masks; the input kinds; region_sizes, bounding_boxes, find_objects and
 remove_small_objects against np.bincount, scipy.ndimage.find_objects and the NumPy expression over SciPy's labels;
-repeatability; guarded memory and a side stream.  The oracle is SciPy on this machine and every comparison is exact."""
+repeatability; a drawn table of structured masks (blobs, strokes, rings, mazes) and the constructed chains at 17 x 17
+tiles; guarded memory and a side stream.  The oracle is SciPy on this machine and every comparison is exact."""
 import functools
 import os
 
@@ -238,6 +239,133 @@ def test_remove_small_objects(gpu_device, connectivity):
     # any input is the mask `!= 0`: an integer raster is not taken as labels
     ints = np.where(masks[1][1], 3, 0).astype(np.int32)
     assert np.array_equal(lb.remove_small_objects(ints, 5, connectivity), lb.remove_small_objects(masks[1][1], 5, connectivity))
+
+
+# ------------------------------------------------------------------------------------------
+# structured masks: solid objects across many seams, objects inside holes, long winding chains
+# ------------------------------------------------------------------------------------------
+# Generator (tests/label_numpy.py), shape (rows and columns from 1, 2, 63..65, 127..129, 191..193, 513, 577), seed and
+# structure.  Each of the four structures with both the E and the S link - where the seam pass skips pairs that jobs next
+# to it join - three times on blobs, every other structure once.  Drawn once from numpy's default_rng(20270207) and kept as
+# a literal, so a failure names its case and replays alone.
+DRAWS = [
+    # id, generator, shape, seed, structure
+    (600, 'blobs', (2, 513), 93, 3),
+    (601, 'blobs', (577, 129), 14, 3),
+    (602, 'blobs', (193, 65), 60, 3),
+    (603, 'blobs', (193, 63), 39, 7),
+    (604, 'blobs', (192, 191), 27, 7),
+    (605, 'blobs', (192, 127), 92, 7),
+    (606, 'blobs', (2, 63), 86, 11),
+    (607, 'blobs', (192, 577), 94, 11),
+    (608, 'blobs', (64, 63), 90, 11),
+    (609, 'blobs', (193, 63), 76, 15),
+    (610, 'blobs', (192, 191), 87, 15),
+    (611, 'blobs', (577, 192), 64, 15),
+    (612, 'strokes', (513, 2), 12, 0),
+    (613, 'rings', (191, 193), 54, 1),
+    (614, 'maze', (65, 1), 21, 2),
+    (615, 'strokes', (129, 64), 15, 4),
+    (616, 'rings', (63, 192), 68, 5),
+    (617, 'maze', (129, 577), 36, 6),
+    (618, 'strokes', (192, 191), 84, 8),
+    (619, 'rings', (65, 129), 2, 9),
+    (620, 'maze', (513, 63), 75, 10),
+    (621, 'strokes', (128, 64), 88, 12),
+    (622, 'rings', (577, 129), 8, 13),
+    (623, 'maze', (128, 64), 86, 14),
+]
+DRAW_AXIS = (1, 2, 63, 64, 65, 127, 128, 129, 191, 192, 193, 513, 577)
+LARGE = (1025, 1030)                      # 17 x 17 tiles
+
+
+def test_the_draws_cover_every_structure():
+    assert len(DRAWS) >= 24 and len({c[0] for c in DRAWS}) == len(DRAWS)
+    assert all(c[2][0] in DRAW_AXIS and c[2][1] in DRAW_AXIS and c[1] in lbn.GENERATORS for c in DRAWS)
+    assert {c[4] for c in DRAWS} == set(range(16))
+    assert {c[1] for c in DRAWS} == set(lbn.GENERATORS)
+    for k in range(16):
+        if k & lbn.E and k & lbn.S:
+            assert sum(c[1] == "blobs" and c[4] == k for c in DRAWS) >= 3, k
+
+
+@pytest.mark.parametrize("case", DRAWS, ids=lambda c: str(c[0]))
+def test_structured_masks_against_scipy(gpu_device, case):
+    """label against SciPy, then sizes, boxes and find_objects on those labels and remove_small_objects on the mask"""
+    lb = _lb()
+    cid, name, shape, seed, k = case
+    mask = lbn.GENERATORS[name](shape, seed)
+    L, n = ndi.label(mask, lbn.STRUCTURES[k])
+    got = lb.label(mask, lbn.STRUCTURES[k])
+    assert_labels(got, (L, n), case)
+    sizes = np.bincount(L.ravel(), minlength=n + 1).astype(np.int64)
+    found = ndi.find_objects(L)
+    assert np.array_equal(lb.region_sizes(got[0], n), sizes), case
+    assert np.array_equal(lb.bounding_boxes(got[0], n), boxes_of(found, n)), case
+    assert lb.find_objects(got[0]) == found, case
+    connectivity = 2 if k & (lbn.SE | lbn.SW) else 1
+    if k not in USUAL:                                      # remove_small_objects knows the two usual structures only
+        L, n = ndi.label(mask, lbn.STRUCTURES[USUAL[connectivity - 1]])
+        sizes = np.bincount(L.ravel(), minlength=n + 1)
+    for min_size in (2, int(np.median(sizes[1:])) if n else 5, 64):
+        keep = lb.remove_small_objects(mask, min_size, connectivity)
+        assert keep.dtype == bool and np.array_equal(keep, lbn.kept(L, sizes, min_size)), (case, min_size)
+
+
+def large_masks():
+    """name -> mask at 17 x 17 tiles: the constructed chains, their transposes (chains along columns cross the other
+    seam) and the maze"""
+    out = {}
+    for name, make in (("serpentine", lbn.serpentine), ("spiral", lbn.spiral), ("comb", lbn.comb)):
+        out[name] = make(LARGE)
+        out[name + " transposed"] = np.ascontiguousarray(make(LARGE[::-1]).T)
+    out["maze"] = lbn.maze(LARGE, 1)
+    return out
+
+
+def _timed(lb, Mt, structure, repeats=5):
+    """the labels of a mask on the device and the median wall time of the call, which ends with the read of the count"""
+    import time
+    import torch
+    times = []
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        L, n = lb.label(Mt, structure)
+        times.append(time.perf_counter() - t0)
+    return (L.cpu().numpy(), n), sorted(times)[repeats // 2]
+
+
+def test_large_constructed_masks_against_scipy(gpu_device, capsys):
+    """1025 x 1030 under the 4- and the 8-neighbourhood; the checkerboard under the 4-neighbourhood, some 528 000
+    objects, so the scan runs over many blocks; the maze three times, bit for bit.  The find-root walks have no path
+    compression, so each mask's wall time is printed beside a Bernoulli mask's of the same size (DESIGN.md section 21
+    keeps the figures; nothing is asserted of them)."""
+    import torch
+    lb = _lb()
+    noise = torch.from_numpy(lbn.random_mask(LARGE, 0.59, 7)).to(gpu_device)
+    lb.label(noise)                                                          # the first call loads the kernels
+    times = {}
+    for k in USUAL:
+        times["random p=0.59", k] = _timed(lb, noise, lbn.STRUCTURES[k])[1]
+    for name, mask in large_masks().items():
+        Mt = torch.from_numpy(mask).to(gpu_device)
+        for k in USUAL:
+            got, times[name, k] = _timed(lb, Mt, lbn.STRUCTURES[k])
+            want = ndi.label(mask, lbn.STRUCTURES[k])
+            assert_labels(got, want, (name, k))
+        if name == "maze":
+            again = [lb.label(Mt) for _ in range(3)]
+            assert [r[1] for r in again] == [1] * 3
+            assert torch.equal(again[0][0], again[1][0]) and torch.equal(again[0][0], again[2][0])
+            assert np.array_equal(again[0][0].cpu().numpy(), ndi.label(mask)[0])
+    board = lbn.checkerboard(LARGE)
+    got, times["checkerboard", lbn.FOUR] = _timed(lb, torch.from_numpy(board).to(gpu_device), lbn.STRUCTURES[lbn.FOUR])
+    assert_labels(got, ndi.label(board), "checkerboard")
+    assert got[1] == (LARGE[0] * LARGE[1] + 1) // 2 > 500000
+    with capsys.disabled():
+        for (name, k), t in times.items():
+            print("\nlabel %s %d x %d, structure %d: %.2f ms (%.1f x random)" % ((name,) + LARGE + (k, 1e3 * t, t / times["random p=0.59", k])), end="")
 
 
 # ------------------------------------------------------------------------------------------

@@ -60,6 +60,33 @@ def test_restatement_equals_scipy():
     assert n == 2 and L[0, 8] == L[2, 2] == 1 and L[1, 5] == 2
 
 
+def test_restatement_equals_scipy_on_the_structured_masks():
+    """blobs, strokes, rings and the maze: a row, a column and a raster each, and what their docstrings promise"""
+    compared = 0
+    for name, make in lbn.GENERATORS.items():
+        for shape in ((1, 1), (1, 37), (41, 1), (2, 2), (23, 38)):
+            for seed in (1, 2):
+                mask = make(shape, seed)
+                assert mask.dtype == bool and mask.shape == shape, (name, shape)
+                assert np.array_equal(mask, make(shape, seed)), (name, shape, "the same mask from the same seed")
+                for k in (lbn.FOUR, lbn.EIGHT, lbn.E | lbn.S | lbn.SE, lbn.S | lbn.SW, 0):
+                    want, n = ndi.label(mask, lbn.STRUCTURES[k])
+                    got, m = lbn.label(mask, lbn.STRUCTURES[k])
+                    assert m == n and np.array_equal(got, want), (name, shape, seed, k)
+                    compared += 1
+    assert compared == 200
+    for seed in (1, 2, 3):
+        M = lbn.maze((65, 130), seed)
+        assert ndi.label(M)[1] == 1 and M[::2, ::2].all() and not M[1::2, 1::2].any()
+        assert M.sum() == 2 * 33 * 65 - 1                                  # a tree: one passage less than cells
+        B = lbn.blobs((65, 130), seed)
+        holes = ndi.label(~B)[1]
+        assert 0.4 < B.mean() < 0.6 and 2 <= ndi.label(B)[1] < 200 and holes >= 2
+        R = lbn.rings((65, 130), seed)
+        assert ndi.label(R, lbn.STRUCTURES[lbn.EIGHT])[1] >= 3
+        assert 0.02 < lbn.strokes((65, 130), seed).mean() < 0.9
+
+
 def test_restatement_on_the_hand_made_labels():
     H = lbn.HAND
     for max_label in (0, 1, 5, 7, 9, 45):
